@@ -12,10 +12,14 @@ range [rank*G, (rank+1)*G) — independent FEC groups, no collective on the data
 path (weak scaling).  Timing: barrier + synchronize on both sides of exactly K
 steps, max over ranks.
 
-Also reported (same JSON line): the encode kernel's roofline (HIP events on
-the stream the kernels run on), the CPU baseline (oracle on host cores, rank 0,
-N=1), the end-to-end pinned-host rate, and the ragged (k 5-15, len 64-1350)
-batch.
+A plain run sets up, warms up, times the K steps and prints the JSON line,
+with the encode kernel's roofline from the HIP events recorded around the
+timed launches (on the stream the kernels run on).  `--dump-outputs DIR`
+writes what the last timed step computed.  `--full` adds, on the same line,
+the check of the timed steps' outputs and every other leg: the CPU baseline
+(oracle on host cores, rank 0, N=1), the end-to-end pinned-host rate, the
+ragged (k 5-15, len 64-1350) batch, packet protection, entropy, the fused and
+connection legs and the measured ceilings.
 """
 from __future__ import annotations
 
@@ -32,6 +36,9 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, MI355X_MICROARCH.md (spec 8.0 TB/s)
 SEED_FIXED, SEED_RAGGED, SEED_DROP = 0x51554943, 0x51554944, 0x51554945
+# --dump-outputs: groups sampled per array (2 arrays x 4096 x L float32: 44 MB
+# at L = 1350, 48 MB at the largest L) and the seed of the sample
+DUMP_GROUPS, SEED_DUMP = 4096, 0x51554946
 
 
 def parse(argv=None):
@@ -44,6 +51,16 @@ def parse(argv=None):
     p.add_argument("--groups", type=int, default=1 << 20, help="FEC groups per GPU")
     p.add_argument("--k", type=int, default=10)
     p.add_argument("--L", type=int, default=1350)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also verify their outputs and run every other "
+                        "leg (one-pass kernel, in-slot recover, beside-service, ceilings, ragged, "
+                        "protect, entropy, fused, host-memory, connection, CPU baseline); the "
+                        "--no-* switches take legs out of a --full run")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed to DIR/parity.npy and "
+                        "DIR/revived.npy (float32, one row per group): every group when there "
+                        f"are at most {DUMP_GROUPS}, else a fixed seeded sample of that many "
+                        "(N>1: one pair per rank, DIR/<name>_rank<r>.npy)")
     p.add_argument("--cached", action="store_true",
                    help="default cache policy instead of nt loads/stores")
     p.add_argument("--one-pass", action="store_true",
@@ -236,6 +253,12 @@ class HipFixedWorkload:
         return [hashlib.sha256(self.par.cpu().numpy().tobytes()).hexdigest()[:32],
                 hashlib.sha256(self.out.cpu().numpy().tobytes()).hexdigest()[:32]]
 
+    def outputs(self, groups):
+        """The given groups' rows of what a caller of step() receives (host, u8)."""
+        idx = self.torch.from_numpy(groups).to(self.dev)
+        return {"parity": self.par.view(self.G, self.L)[idx].cpu().numpy(),
+                "revived": self.out.view(self.G, self.L)[idx].cpu().numpy()}
+
     def host_rows(self):
         return self.rows.cpu().numpy()
 
@@ -293,11 +316,36 @@ class CpuStandInWorkload:
         return [hashlib.sha256(self.par.tobytes()).hexdigest()[:32],
                 hashlib.sha256(self.out.tobytes()).hexdigest()[:32]]
 
+    def outputs(self, groups):
+        return {"parity": self.par.reshape(self.G, self.L)[groups],
+                "revived": self.out.reshape(self.G, self.L)[groups]}
+
     def host_rows(self):
         return self.rows
 
     def release(self):
         pass
+
+
+def dump_groups(G):
+    """The groups --dump-outputs writes: all of them up to DUMP_GROUPS, else a
+    fixed sample of that many (seeded, ascending, both ends included) -- the
+    same for every run of the same --groups."""
+    if G <= DUMP_GROUPS:
+        return np.arange(G, dtype=np.int64)
+    idx = np.sort(np.random.default_rng(SEED_DUMP).choice(G, DUMP_GROUPS, replace=False))
+    idx[0], idx[-1] = 0, G - 1
+    return idx.astype(np.int64)
+
+
+def dump_outputs(work, dirname, rank, world):
+    """--dump-outputs: the parity and the revived packets the last timed step
+    wrote (the outputs were poisoned before the timed steps), one row of L
+    byte values per dumped group, as float32 .npy files."""
+    os.makedirs(dirname, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    for name, a in work.outputs(dump_groups(work.G)).items():
+        np.save(os.path.join(dirname, f"{name}{tag}.npy"), a.astype(np.float32))
 
 
 def timed_steps(work, steps, warmup, barrier, reduce_max):
@@ -697,7 +745,11 @@ def main(argv=None):
                                 one_pass=args.one_pass)
     elapsed, events = timed_steps(work, args.steps, args.warmup, barrier, reduce_max)
     enc_s, rec_s = work.kernel_seconds(events)
-    verified = None if args.no_verify else work.verify()
+    if args.dump_outputs:
+        dump_outputs(work, args.dump_outputs, rank, world)
+    # the outputs are checked in a --full run and where the line lists the
+    # shards (--digests, --cpu-workload: each entry says whether it verified)
+    verified = work.verify() if (args.full or cpu or args.digests) and not args.no_verify else None
     per_rank = gather({"rank": rank, "g0": g0, "groups": G, "enc_s": enc_s, "rec_s": rec_s,
                        "verified": verified,
                        "digests": work.digests() if (cpu or args.digests) else None,
@@ -720,7 +772,7 @@ def main(argv=None):
         line["roofline"]["per_rank_frac"] = {"min": round(min(fr), 4), "max": round(max(fr), 4)}
     if world > 1:
         line["control_plane"] = "gloo (CPU tensors): barrier, max, gather; no data collective"
-    if world > 1 and not cpu and not args.no_e2e and not args.profile_only:
+    if args.full and world > 1 and not cpu and not args.no_e2e and not args.profile_only:
         # the host-memory path on every rank at once: each
         # GPU's pinned buffers on its own NUMA node, its own PCIe link
         barrier()
@@ -751,7 +803,9 @@ def main(argv=None):
         line["note_shared_device"] = ("QFEC_BENCH_SHARE_DEVICE: all ranks on cuda:0 (a test of the "
                                       "N>1 path, not a scaling measurement)")
 
-    extras = rank == 0 and world == 1 and not cpu and not args.profile_only
+    # every leg below is part of a --full run only: a plain run has timed its
+    # steps and prints the line
+    extras = args.full and rank == 0 and world == 1 and not cpu and not args.profile_only
     if rank == 0 and world == 1 and not cpu and args.profile_only and not args.no_ragged:
         # the ragged kernels' launches for the rocprofv3 runs (tools/pmc.sh)
         work.release()
@@ -796,7 +850,8 @@ def main(argv=None):
     # The CPU baseline: rank 0 at N=1 only, after the timed region, over the
     # same workload (an N>1 line carries cpu_baseline null: the N=1 line has it).
     host_rows = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_only:
+    if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+            and not args.profile_only):
         host_rows = work.host_rows()
     if extras:
         work.release()

@@ -1,7 +1,8 @@
 """ctypes binding of integration/connection_shim.cc (fec_conn_run): client /
 server pairs of the patched reference QuicConnection at QUIC_VERSION_31 over
 a lossy in-memory writer, FEC on the GPU.  Test / bench infrastructure: the
-library is integration/_build/libquic_fec_patched.so (integration/build.py).
+library is oracle/_ref/integration/libquic_fec_patched.so
+(oracle/ref_integration.py).
 """
 from __future__ import annotations
 
@@ -9,10 +10,11 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB = os.path.join(HERE, "_build", "libquic_fec_patched.so")
+_OUT = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "integration")
+LIB = os.path.join(_OUT, "libquic_fec_patched.so")
 # the same build over tests/cpp/cpu_qfec_stub.c (CPU parity in place of the
 # GPU): lets the CPU suite run the connection path's FEC end to end
-LIB_CPU = os.path.join(HERE, "_build", "libquic_fec_patched_cpustub.so")
+LIB_CPU = os.path.join(_OUT, "libquic_fec_patched_cpustub.so")
 
 
 class Params(C.Structure):
@@ -54,7 +56,7 @@ def lib(cpu_stub=False):
     path = LIB_CPU if cpu_stub else LIB
     if path not in _libs:
         if not os.path.exists(path):
-            raise RuntimeError(f"{path} missing: build it with python integration/build.py")
+            raise RuntimeError(f"{path} missing: build it with python -m oracle.ref_integration")
         h = C.CDLL(path)
         h.fec_conn_run.restype = C.c_int
         h.fec_conn_run.argtypes = [C.POINTER(Params), C.POINTER(Result)]

@@ -6,7 +6,7 @@
 // -> the FEC hooks -> SendOrQueuePacket -> QuicPacketWriter), with the XOR on
 // the GPU (libqfec.so).
 //
-// Built by integration/build.py into integration/_build/libquic_fec_patched.so
+// Built by oracle/ref_integration.py into oracle/_ref/integration/libquic_fec_patched.so
 // with quic_connection.cc and everything it reaches compiled from
 // /root/reference (no stand-ins).  What the harness supplies is what a
 // libquic embedder supplies (quic_connection.h:275-287, quic_alarm_factory.h,

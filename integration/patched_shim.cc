@@ -2,7 +2,7 @@
 // the REFERENCE's QuicPacketCreator and QuicFramer, patched, sending and
 // receiving a FEC-protected QUIC_VERSION_31 stream through the MI355X FEC path.
 //
-// Built by integration/build.py into integration/_build/libquic_fec_patched.so
+// Built by oracle/ref_integration.py into oracle/_ref/integration/libquic_fec_patched.so
 // together with the patched reference sources and the FEC host code
 // (-DQFEC_WITH_LIBQUIC); the XOR runs in libqfec.so on the GPU.
 //

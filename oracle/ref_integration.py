@@ -2,8 +2,8 @@
 build them together with the MI355X FEC host code — the drop-in check
 (INTEGRATION.md).
 
-  1. copy the patched files' originals from /root/reference/src into
-     integration/_build/src (never into the repository: _build/ is
+  1. copy the patched files' originals from the reference's src/ into
+     oracle/_ref/integration/src (never into the repository: oracle/_ref/ is
      git-ignored) and apply the patch with `patch -p1`, as the reference's own
      patch/ convention does;
   2. drop libquic_amd/csrc/quic_fec_{group,wire,connection}.{h,cc} into
@@ -14,14 +14,15 @@ build them together with the MI355X FEC host code — the drop-in check
   4. link the patched framer + packet creator + QuicConnection + the FEC host
      code + what they reach in the reference tree (packet generator, packet
      managers, congestion control, config, base/metrics: -z defs, no
-     stand-ins) into integration/_build/libquic_fec_patched.so (C API:
+     stand-ins) into oracle/_ref/integration/libquic_fec_patched.so (C API:
      integration/patched_shim.cc — creator + framer — and
      integration/connection_shim.cc — QuicConnection pairs over a lossy
      in-memory writer), GPU work through libqfec.so.
 
-Only where /root/reference exists (this container); the built .so travels to
-the GPU box with the tree (git-ignored, not gpurun-ignored) for the
-end-to-end GPU test (tests/test_integration.py).
+Only where the reference tree exists; the built libraries live under
+oracle/_ref/ with the other reference builds, which is what a machine
+without the reference tree is given, so the end-to-end GPU tests
+(tests/test_integration.py, tests/test_connection_e2e.py) find them there.
 """
 from __future__ import annotations
 
@@ -31,10 +32,10 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.join(ROOT, "integration")  # the patch and the shims
 REF = os.environ.get("QFEC_REFERENCE", "/root/reference")
-OUT = os.path.join(HERE, "_build")
+OUT = os.path.join(ROOT, "oracle", "_ref", "integration")
 SRC = os.path.join(OUT, "src")
 CORE = os.path.join(SRC, "net", "quic", "core")
 PATCH = os.path.join(HERE, "libquic_fec.patch")
@@ -59,7 +60,7 @@ SYNTAX_UNITS = ["quic_protocol.cc", "quic_framer.cc", "quic_packet_creator.cc",
                 "quic_connection.cc", "quic_received_packet_manager.cc",
                 "quic_sent_packet_manager.cc", "quic_fec_group.cc", "quic_fec_wire.cc",
                 "quic_fec_connection.cc"]
-# linked: the patched units + the FEC host code (from _build) and, unmodified
+# linked: the patched units + the FEC host code (from OUT) and, unmodified
 # from the reference tree, what the framer and the packet creator reach
 LINK_PATCHED = ["quic_protocol.cc", "quic_framer.cc", "quic_packet_creator.cc",
                 "quic_connection.cc", "quic_connection_stats.cc",
@@ -203,7 +204,7 @@ def build_lib() -> str:
     libdir = os.path.join(ROOT, "libquic_amd")
     subprocess.run(["g++", "-shared", "-pthread", "-Wl,--gc-sections", "-Wl,-z,defs", "-Wl,-Bsymbolic",
                     "-o", LIB + ".tmp", *objs, "-L", libdir, "-lqfec",
-                    "-Wl,-rpath,$ORIGIN/../../libquic_amd", "-Wl,-rpath-link,/opt/rocm/lib"],
+                    "-Wl,-rpath,$ORIGIN/../../../libquic_amd", "-Wl,-rpath-link,/opt/rocm/lib"],
                    check=True)
     os.replace(LIB + ".tmp", LIB)
     stub = _obj(STUB, ["gcc", "-std=c11", "-O2", "-fPIC", "-fvisibility=hidden", "-I",
@@ -216,8 +217,8 @@ def build_lib() -> str:
 
 def regen_patch() -> str:
     """Maintainer step: rewrite integration/libquic_fec.patch from the edited
-    copies under _build/src (after prepare() and edits there), one
-    `diff -u` per PATCHED file against /root/reference, in file name order."""
+    copies under OUT/src (after prepare() and edits there), one
+    `diff -u` per PATCHED file against the reference, in file name order."""
     out = []
     for f in sorted(PATCHED):
         rel = f"src/net/quic/core/{f}"
@@ -253,5 +254,5 @@ if __name__ == "__main__":
         print("rewrote", regen_patch())
         sys.exit(0)
     ok = build()
-    print("integration build:", "ok" if ok else "skipped (no /root/reference)")
+    print("integration build:", "ok" if ok else "skipped (no reference tree)")
     sys.exit(0)

@@ -19,7 +19,7 @@ import pytest
 
 from conftest import ROOT
 
-LIB = os.path.join(ROOT, "integration", "_build", "libquic_fec_patched.so")
+LIB = os.path.join(ROOT, "oracle", "_ref", "integration", "libquic_fec_patched.so")
 U64P = C.POINTER(C.c_uint64)
 
 

@@ -29,8 +29,9 @@ import pytest
 
 from conftest import ROOT
 
-LIB = os.path.join(ROOT, "integration", "_build", "libquic_fec_patched.so")
-LIB_CPU = os.path.join(ROOT, "integration", "_build", "libquic_fec_patched_cpustub.so")
+LIB = os.path.join(ROOT, "oracle", "_ref", "integration", "libquic_fec_patched.so")
+LIB_CPU = os.path.join(ROOT, "oracle", "_ref", "integration",
+                       "libquic_fec_patched_cpustub.so")
 
 # backend of the FEC cases: the GPU, or the CPU stub build
 BACKENDS = [pytest.param(False, marks=pytest.mark.gpu, id="gpu"),
@@ -40,7 +41,7 @@ BACKENDS = [pytest.param(False, marks=pytest.mark.gpu, id="gpu"),
 def _harness(cpu_stub=False):
     if not os.path.exists(LIB_CPU if cpu_stub else LIB):
         if os.path.isdir("/root/reference/src/net/quic/core"):
-            pytest.fail(f"{LIB} missing: python integration/build.py")
+            pytest.fail(f"{LIB} missing: python -m oracle.ref_integration")
         pytest.skip("the patched reference library is built where /root/reference is")
     import importlib.util
     spec = importlib.util.spec_from_file_location(

@@ -151,7 +151,7 @@ def test_bench_cli_two_ranks_on_one_gpu():
         pytest.fail("GPU test selected but no HIP device is visible")
     G = 1 << 16
     p = _bench_cli(["--gpus", "2", "--groups", str(G), "--steps", "3", "--warmup", "1",
-                    "--one-pass", "--digests", "--no-cpu-baseline"],
+                    "--one-pass", "--digests", "--no-cpu-baseline", "--full"],
                    env_extra={"QFEC_BENCH_SHARE_DEVICE": "1"}, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

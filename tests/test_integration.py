@@ -6,9 +6,9 @@ translation unit — quic_protocol, quic_framer, quic_packet_creator,
 quic_connection — plus the FEC host code built against the reference's types
 (-DQFEC_WITH_LIBQUIC) compiles (g++ -fsyntax-only), and the patched framer +
 packet creator + FEC host code LINK with the rest of what they need from the
-reference tree (-z defs): integration/build.py.
+reference tree (-z defs): oracle/ref_integration.py.
 
-GPU: integration/_build/libquic_fec_patched.so — the patched reference
+GPU: oracle/_ref/integration/libquic_fec_patched.so — the patched reference
 QuicPacketCreator sends a FEC-protected QUIC_VERSION_31 stream (FEC packets
 from the GPU parity), one data packet in N is dropped, the patched reference
 QuicFramer receives the rest and the revived packets (GPU revive, then
@@ -23,16 +23,12 @@ import pytest
 from conftest import ROOT
 
 INTEG = os.path.join(ROOT, "integration")
-LIB = os.path.join(INTEG, "_build", "libquic_fec_patched.so")
+LIB = os.path.join(ROOT, "oracle", "_ref", "integration", "libquic_fec_patched.so")
 
 
 def _builder():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("integration_build",
-                                                  os.path.join(INTEG, "build.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    from oracle import ref_integration
+    return ref_integration
 
 
 def test_patch_names_only_the_hook_files():
@@ -79,7 +75,7 @@ class E2E(C.Structure):
 
 def _run(group_size, stream_len, drop_every):
     if not os.path.exists(LIB):
-        pytest.fail(f"{LIB} missing: build it with python integration/build.py")
+        pytest.fail(f"{LIB} missing: build it with python -m oracle.ref_integration")
     lib = C.CDLL(LIB)
     lib.fec_e2e_run.restype = C.c_int
     lib.fec_e2e_run.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(E2E)]

@@ -12,4 +12,4 @@ timeout -k 10 200 tools/tune/build/host_cost 64 1024 4096 16384 > "$OUT/host_cos
 timeout -k 10 120 tools/tune/build/pcie_duplex 1024 7 > "$OUT/pcie_duplex.txt" 2>&1 &&
 HSA_ENABLE_SDMA=0 timeout -k 10 120 tools/tune/build/pcie_duplex 1024 7 > "$OUT/pcie_duplex_nosdma.txt" 2>&1 &&
 timeout -k 10 300 python -u -c "import bench, json; print(json.dumps(bench.bench_connection_e2e()))" > "$OUT/conn_e2e.txt" 2>&1 &&
-timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" && tail -c 1500 "$OUT/bench.json"
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" && tail -c 1500 "$OUT/bench.json"

@@ -19,7 +19,7 @@ for s in $STEPS; do
         > "$OUT/phase_k_table.txt" 2>&1 || { tail -n 30 "$OUT/phase_k_table.txt"; exit 1; }
       tail -n 22 "$OUT/phase_k_table.txt" ;;
     bench)
-      timeout -k 10 900 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -n 30 "$OUT/bench.err"; exit 1; }
+      timeout -k 10 900 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -n 30 "$OUT/bench.err"; exit 1; }
       tail -c 1500 "$OUT/bench.json" ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac

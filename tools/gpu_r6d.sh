@@ -15,7 +15,7 @@ timeout -k 10 300 python -u tools/phase_reserve_ab.py 6 5 > "$OUT/phase_reserve_
 cat "$OUT/phase_reserve_ab.txt" &&
 timeout -k 10 600 python -u tools/phase_k_table.py 5 8 10,17,20,24,32,48,64,128,255 > "$OUT/phase_k_table.txt" 2>&1 &&
 tail -13 "$OUT/phase_k_table.txt" &&
-timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 --no-ragged --no-protect --no-entropy \
+timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 --no-ragged --no-protect --no-entropy \
   --no-fused --no-e2e --no-cpu-baseline --no-ceilings > "$OUT/bench.json" 2> "$OUT/bench.err" &&
 timeout -k 10 300 tools/tune/build/tune_rblock 10 4 16 1536 1 > "$OUT/tune_rblock_diag.txt" 2>&1
 tail -12 "$OUT/tune_rblock_diag.txt" &&

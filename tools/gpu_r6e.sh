@@ -17,7 +17,7 @@ cat "$OUT/tune_aes_bitslice.txt"
 [ $rc2 -le 2 ] || exit $rc2
 timeout -k 10 300 tools/tune/build/tune_rblock 10 5 16 1536 1 > "$OUT/tune_rblock_diag.txt" 2>&1 &&
 tail -14 "$OUT/tune_rblock_diag.txt" &&
-timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 --no-ragged --no-protect --no-entropy \
+timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 --no-ragged --no-protect --no-entropy \
   --no-fused --no-e2e --no-cpu-baseline --no-ceilings --no-connection > "$OUT/bench.json" 2> "$OUT/bench.err" &&
 grep -o '"phase_beside_service": {[^}]*}' "$OUT/bench.json"
 rc3=$?

@@ -13,7 +13,7 @@ tail -3 "$OUT/pytest_service.log"
 [ $rc -le 1 ] || exit $rc
 timeout -k 10 300 python -u tools/svc_trace.py 300 > "$OUT/svc_trace.txt" 2>&1 &&
 cat "$OUT/svc_trace.txt" &&
-timeout -k 10 400 python -u bench.py --steps 4 --warmup 2 --no-ragged --no-protect --no-entropy \
+timeout -k 10 400 python -u bench.py --full --steps 4 --warmup 2 --no-ragged --no-protect --no-entropy \
   --no-fused --no-e2e --no-cpu-baseline --no-ceilings --no-beside-service > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc3=$?
 grep -o '"connection": {.\{0,900\}' "$OUT/bench.json" | head -c 1200

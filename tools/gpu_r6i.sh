@@ -12,7 +12,7 @@ tail -3 "$OUT/pytest.log"; grep "abandoned" "$OUT/pytest.log"
 [ $rc -le 1 ] || exit $rc
 timeout -k 10 600 python -u tools/phase_k_table.py 5 8 16,17,20,24 > "$OUT/phase_k_table.txt" 2>&1 &&
 tail -8 "$OUT/phase_k_table.txt" &&
-timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 --no-ragged --no-protect --no-entropy \
+timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 --no-ragged --no-protect --no-entropy \
   --no-fused --no-e2e --no-cpu-baseline --no-ceilings --no-connection > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc3=$?
 grep -o '"phase_beside_service": {[^}]*}' "$OUT/bench.json"
