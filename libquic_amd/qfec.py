@@ -523,7 +523,9 @@ class Context:
         return self._check(self.lib.qfec_debug_phase_reserve(self.ctx, cus))
 
     def debug_phase_rtbatch(self, batch):
-        """Test hook: the runtime-k phased body's load batch (16, 32; 0 = default 32)."""
+        """Test hook: the runtime-k phased body's load batch (16, 32; 0 = the
+        default by operation: encode and in place 16, recover 32 up to
+        k = 32 and 16 above)."""
         return self._check(self.lib.qfec_debug_phase_rtbatch(self.ctx, batch))
 
     def complete(self, wait=True):

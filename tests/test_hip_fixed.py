@@ -67,15 +67,22 @@ def test_golden_shapes(ctx, golden_shapes):
         assert np.array_equal(out.reshape(n, L), golden_shapes[f"{tag}_recovered"]), tag
 
 
-@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 8, 9, 10, 11, 16, 17, 33, 255])
-@pytest.mark.parametrize("L", [1, 7, 15, 16, 17, 31, 100, 1350, 1452])
-def test_vs_oracle_k_L(ctx, k, L):
+# every templated group size (1..16: each its own compiled one-pass bodies),
+# the runtime-k body above them, under both cache policies (QFEC_CACHED
+# compiles a second copy of every body); the default policy keeps the "L-k" ids
+@pytest.mark.parametrize(
+    "L,k,cached",
+    [pytest.param(L, k, cached, id=f"{L}-{k}" + ("-cached" if cached else ""))
+     for cached in (False, True)
+     for k in list(range(1, 18)) + [33, 255]
+     for L in [1, 7, 15, 16, 17, 31, 100, 1350, 1452]])
+def test_vs_oracle_k_L(ctx, k, L, cached):
     n = 7 if k < 100 else 2
     rows = OC.synth_fixed(0xABC + k, 11, n, k, L)
     miss = Q.drop_index(Q.SEED_DROP, np.arange(11, 11 + n), k).astype(np.uint8)
     _, want_p = OC.encode_fixed(rows, k, L, n)
     _, want_o = OC.recover_fixed(rows, want_p, miss, k, L, n)
-    par, out = run_fixed(ctx, rows, k, L, n, miss)
+    par, out = run_fixed(ctx, rows, k, L, n, miss, cached=cached)
     assert np.array_equal(par, want_p)
     assert np.array_equal(out, want_o)
 
