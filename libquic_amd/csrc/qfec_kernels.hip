@@ -297,7 +297,6 @@ constexpr int kPhSteps = 40;         // 40 x 256 lanes x 16 B = 160 KiB of LDS
 // profiles/round3/phase/tune_phase_rs*.txt; 40 + 40 / 48 / 64 spill into
 // AGPRs and lose).
 constexpr int kPhRegSteps = 32;
-constexpr int kPhUDefault = 1;       // steps loaded together (k loads in flight per lane)
 constexpr uint64_t kPhTimeout = 20000;  // s_memrealtime ticks (100 MHz): 200 us
 
 // sync words, 256 B apart: [0] top, [1..16] sub-counters, [17] exits, [18] abandon,
@@ -354,118 +353,124 @@ __device__ __forceinline__ void phase_exit(uint32_t* ps, uint32_t* host) {
   }
 }
 
-// Defaults = the product (tools/tune/tune_phase.hip, profiles/round2/phase/
-// tune_phase8.txt): one meeting per phase, before the stores (MEET2 adds one
-// after them: -3%), one step's k loads in flight per lane (kPhU = 2: -4%);
-// FLAT (row pointers as generic pointers: flat loads) changes nothing; XCDW
-// (XCD-aware order in the window) +0.5% encode / -3% recover; PARFIRST
-// (recover, templated k: the phase's parity rows first, then only the
-// received rows) +2.7% recover (tune_phase12.txt); COMPACT (with PARFIRST: the
-// k-1 received rows loaded in order, r + (r >= m), so no load instruction runs
-// with the lost row's lanes masked off: 17 loads and 22 exec branches per step
-// instead of 18 and 32) +2.5% recover, 0.780 vs 0.761 on six buffer pairs
-// (profiles/round2/phase/tune_phase_compact.txt).
-// RS (encode, tools/tune): RS more steps per phase held in registers after the
-// STEPS LDS ones (a longer phase, fewer meetings; one wave per SIMD leaves the
-// register file to spare).
-template <int KC, bool RECOVER, bool MEET2 = false, bool FLAT = false, int kPhU = kPhUDefault,
-          int STEPS = kPhSteps, int NTHR = kBlock, bool XCDW = false, bool PARFIRST = true,
-          bool NTLD = true, bool EDGE = false, bool COMPACT = true, int RS = 0, bool RPF = false,
-          bool RPFE = false, bool INPL = false, int RTB = 32>
-__global__ __launch_bounds__(NTHR) void phase_xor_kernel(FixedArgs a, uint32_t C, uint32_t gpb,
-                                                           uint32_t nphase) {
+// One phase of one workgroup: the first kPhSteps steps keep their parity in
+// LDS, RS more (templated k only) in registers; a step is gpb groups, its k
+// row loads (nontemporal) in flight per lane, one step at a time.  The grid
+// meets once, then every workgroup stores the phase's parity rows.  Step i of
+// phase p covers one contiguous window of B x gpb groups (the fixed kernel's
+// sliding window), workgroup b its gpb groups at b x gpb.
+//   encode, templated k: the k rows of a step loaded together, XORed.
+//   recover, templated k: the phase's parity rows first, as one stream over
+//     the parity buffer (LDS steps into LDS, then the register steps' into
+//     registers), then per step the k-1 received rows in order, r + (r >= m),
+//     so no load instruction runs with the lost row's lanes masked off.
+//   runtime k (> 16, or > 25 for recover): batches of up to RTB loads in
+//     flight, as even as possible (xor_rows_rt); recover loads the parity in
+//     place of the lost row (parity first with compact received rows measured
+//     2-6% slower for k = 17-48, profiles/round6/phase_k_table_r6c.txt
+//     against r6b).
+//   INPL: the encode form over the k rows of a group whose lost row holds
+//     zeroes, the result written into that row.
+// Which of these a launch gets is phase_body()'s decision, below.
+//
+// Variants measured and removed (tools/tune/tune_phase.hip of that time; the
+// kernel with all of them as template switches is in git history at 2677a57).
+// profiles/round2/phase/tune_phase8.txt: a second meeting per phase, after the
+// stores (MEET2) -3%; two steps' loads in flight per lane (kPhU = 2) -4%; row
+// pointers as generic pointers, flat loads (FLAT) no change; XCD-aware block
+// order in the window (XCDW) +0.5% encode / -3% recover.  Other lanes x steps
+// (NTHR, STEPS) against 256 x 40's 0.79-0.81: 512 x 20 0.74, 1024 x 10 0.68
+// (tune_phase9.txt), 128 x 80 0.50, 192 x 53 0.77 (tune_phase10.txt).
+// tune_phase12.txt: recover's parity rows first (PARFIRST) +2.7% over the
+// parity loaded in place of the lost row.  tune_phase_compact.txt: the compact
+// received rows (COMPACT) +2.5% over every row's load with the lost row's
+// lanes masked off (17 loads and 22 exec branches per step instead of 18 and
+// 32), 0.780 vs 0.761 on six buffer pairs.  Default-policy loads everywhere
+// (NTLD off) -3%, 0.755-0.790 vs 0.781-0.811 (tune_phase13.txt), or only in a
+// row's first and last 128-B line (EDGE) as slow, 0.761-0.784
+// (tune_phase14.txt); DESIGN.md §5.
+// profiles/round3/phase/tune_phase_rs{4,5}.txt: recover's register steps
+// loading each parity row with its step instead of all of them first (RPF
+// off) 0.798-0.805 / 0.793-0.798 vs 0.801-0.808 / 0.797-0.803.
+// profiles/round4/tune_phase_recover_r4l.txt: the register steps' parity rows
+// right after the LDS steps' ones, one parity stream per phase (RPFE), 0.789
+// vs 0.791.
+template <int KC, bool RECOVER, int RS = 0, bool INPL = false, int RTB = 32>
+__global__ __launch_bounds__(kBlock) void phase_xor_kernel(FixedArgs a, uint32_t C, uint32_t gpb,
+                                                             uint32_t nphase) {
   static_assert(!(INPL && RECOVER), "in place: the encode form over the k rows");
-  // (the runtime-k body loads the parity in place of the lost row: parity
-  // first with its received rows compact measured 2-6% slower for k = 17-48,
-  // profiles/round6/phase_k_table_r6c.txt against r6b)
-  constexpr bool PF = RECOVER && PARFIRST && KC > 0;
-  static_assert(!RECOVER || STEPS <= 64, "recover: bad-step masks are 64 bits");
-  static_assert(RS == 0 || (KC > 0 && kPhU == 1 && !XCDW && RS <= 64 &&
-                            (!RECOVER || (PARFIRST && COMPACT))),
-                "register steps: templated k, one step at a time (recover: parity first, compact)");
-  constexpr int TS = STEPS + RS;  // steps per phase (at most)
+  static_assert(kPhSteps <= 64, "recover: bad-step masks are 64 bits");
+  static_assert(RS == 0 || (KC > 0 && RS <= 64), "register steps: templated k, 64-bit lane-on mask");
+  constexpr bool PF = RECOVER && KC > 0;  // parity rows first, compact received rows
+  constexpr int TS = kPhSteps + RS;       // steps per phase (at most)
   // the launch's steps per phase (launch_fixed spreads the batch evenly over
   // its phases, so the last phase is not a sliver); the LDS steps come first
-  const int SP = (kPhU == 1 && a.phase_steps != 0u) ? min((int)a.phase_steps, TS) : TS;
-  const int NL = min(STEPS, SP);  // LDS steps in use
-  __shared__ u32x4 s_par[STEPS][NTHR];  // lane tid's parity of each step
+  const int SP = a.phase_steps != 0u ? min((int)a.phase_steps, TS) : TS;
+  const int NL = min(kPhSteps, SP);  // LDS steps in use
+  __shared__ u32x4 s_par[kPhSteps][kBlock];  // lane tid's parity of each step
   const uint32_t tid = threadIdx.x, gl = tid / C, t = tid - gl * C;
   const bool lane_on = gl < gpb;
   const uint32_t off = min(t * 16u, a.L - 16u);
   const uint32_t k = KC > 0 ? (uint32_t)KC : a.k;
   const uint64_t B = gridDim.x;
   for (uint32_t p = 0; p < nphase; ++p) {
-    // the kPhU steps from i of phase p cover one contiguous window of
-    // B x kPhU gpb groups (the fixed kernel's sliding window); workgroup b
-    // owns kPhU gpb of them
-    // XCDW: the workgroups of one XCD (b, b+8, ...) take one contiguous share
-    // of the window, so the lines two neighbouring groups share stay in one L2
-    const uint64_t wb = XCDW ? xcd_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const uint64_t base = ((uint64_t)p * (uint64_t)(SP / kPhU) * B + wb) * (gpb * kPhU) + gl;
+    const uint64_t base = ((uint64_t)p * (uint64_t)SP * B + blockIdx.x) * gpb + gl;
     // recover: steps whose lost-slot index is out of range (bit i of lo/hi:
-    // 32-bit shifts only, STEPS <= 64)
+    // 32-bit shifts only)
     uint32_t bad_lo = 0, bad_hi = 0;
-    auto gidx = [&](int i) {
-      return base + (uint64_t)(i / kPhU) * B * gpb * kPhU + (uint64_t)(i % kPhU) * gpb;
-    };
+    auto gidx = [&](int i) { return base + (uint64_t)i * B * gpb; };
     // recover: the lost-slot indices of the next steps are loaded one
     // iteration ahead (every row address depends on them)
     uint32_t m_reg[RS > 0 && RECOVER ? RS : 1];  // register steps' lost slots, loaded early
     if constexpr (RS > 0 && RECOVER) {
 #pragma unroll
       for (int j = 0; j < RS; ++j) {
-        const uint64_t g = gidx(STEPS + j);
-        m_reg[j] = lane_on && g < a.n_groups && STEPS + j < SP ? a.missing[g] : 0u;
+        const uint64_t g = gidx(kPhSteps + j);
+        m_reg[j] = lane_on && g < a.n_groups && kPhSteps + j < SP ? a.missing[g] : 0u;
       }
     }
-    uint32_t m_next[kPhU];
+    // The LDS steps go one at a time, in the shape the loop had when U steps'
+    // loads could be in flight together (U = 2 measured -4%, above): with the
+    // one-element arrays as scalars and the one-trip loops gone the compiler
+    // lays the loop's blocks out differently (a branch's sense flips in every
+    // instantiation, registers move in the runtime-k recover), and the code
+    // that was measured is the code that is kept.
+    constexpr int U = 1;
+    uint32_t m_next[U];
     if constexpr (RECOVER) {
 #pragma unroll
-      for (int u = 0; u < kPhU; ++u) {
+      for (int u = 0; u < U; ++u) {
         const uint64_t g = gidx(u);
         m_next[u] = lane_on && g < a.n_groups ? a.missing[g] : 0u;
       }
     }
-    // RPFE (tools/tune): the register steps' parity rows too, right after the
-    // LDS steps' ones -- the phase's whole parity range as one stream
     u32x4 racc[RS > 0 ? RS : 1];
-    static_assert(!RPFE || (RS > 0 && RECOVER && RPF && PF), "RPFE: recover register steps, RPF");
     if constexpr (PF) {
-      // PARFIRST: the phase's parity rows first, into the accumulators (one
-      // stream over the parity buffer), then the received rows only
+      // the LDS steps' parity rows, into the accumulators
 #pragma unroll 1
-      for (int i = 0; i < STEPS; i += 8) {
+      for (int i = 0; i < kPhSteps; i += 8) {
         u32x4 w[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const uint64_t g = gidx(i + j < NL ? i + j : 0);
           const bool on = i + j < NL && lane_on && g < a.n_groups;
-          w[j] = ld16t<NTLD>(a.parity + (on ? g : 0) * a.parity_stride + off);
+          w[j] = ld16t<true>(a.parity + (on ? g : 0) * a.parity_stride + off);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          if (i + j < STEPS) s_par[i + j][tid] = w[j];
-      }
-      if constexpr (RPFE) {
-#pragma unroll
-        for (int j = 0; j < RS; ++j) {
-          const uint64_t g = gidx(STEPS + j);
-          const bool on = lane_on && g < a.n_groups && STEPS + j < SP;
-          racc[j] = ld16t<NTLD>(a.parity + (on ? g : 0) * a.parity_stride + off);
-        }
+          if (i + j < kPhSteps) s_par[i + j][tid] = w[j];
       }
     }
 #pragma unroll 1
-    for (int i = 0; i < NL; i += kPhU) {
-      u32x4 acc[kPhU];
-      uint32_t m[kPhU];
-      const uint8_t* src[kPhU];
+    for (int i = 0; i < NL; i += U) {
+      u32x4 acc[U];
+      uint32_t m[U];
+      const uint8_t* src[U];
 #pragma unroll
-      for (int u = 0; u < kPhU; ++u) {
+      for (int u = 0; u < U; ++u) {
         const uint64_t g = gidx(i + u);
         const bool on = lane_on && g < a.n_groups;
         src[u] = a.rows + (on ? g : 0) * a.group_stride + off;
-        if constexpr (FLAT) asm volatile("" : "+v"(src[u]));
         acc[u] = u32x4{0u, 0u, 0u, 0u};
         m[u] = k;  // encode: no slot replaced
         if constexpr (RECOVER) {
@@ -479,102 +484,70 @@ __global__ __launch_bounds__(NTHR) void phase_xor_kernel(FixedArgs a, uint32_t C
           }
         }
       }
-      if constexpr (PF) {
 #pragma unroll
-        for (int u = 0; u < kPhU; ++u) {
+      for (int u = 0; u < U; ++u) {
+        if constexpr (PF) {
+          // the k-1 received rows in order, every lane on every load
           u32x4 v[KC];
-          if constexpr (COMPACT) {
-            // the k-1 received rows in order, every lane on every load (no
-            // instruction with the lost row's lanes masked off)
 #pragma unroll
-            for (int r = 0; r + 1 < KC; ++r)
-              v[r] = ld16t<NTLD>(src[u] + ((uint32_t)r + ((uint32_t)r >= m[u] ? 1u : 0u)) * a.row_stride);
-            v[KC - 1] = u32x4{0u, 0u, 0u, 0u};
-          } else {
-#pragma unroll
-            for (int r = 0; r < KC; ++r) {
-              v[r] = u32x4{0u, 0u, 0u, 0u};
-              if ((uint32_t)r != m[u]) v[r] = ld16t<NTLD>(src[u] + r * a.row_stride);
-            }
-          }
+          for (int r = 0; r + 1 < KC; ++r)
+            v[r] = ld16t<true>(src[u] + ((uint32_t)r + ((uint32_t)r >= m[u] ? 1u : 0u)) * a.row_stride);
+          v[KC - 1] = u32x4{0u, 0u, 0u, 0u};
           acc[u] = s_par[i + u][tid];
 #pragma unroll
           for (int r = 0; r < KC; ++r) acc[u] ^= v[r];
-        }
-      } else if constexpr (KC > 0) {
-        u32x4 v[kPhU][KC];
+        } else if constexpr (KC > 0) {
+          u32x4 v[KC];
 #pragma unroll
-        for (int u = 0; u < kPhU; ++u) {
+          for (int r = 0; r < KC; ++r) v[r] = ld16t<true>(src[u] + r * a.row_stride);
+#pragma unroll
+          for (int r = 0; r < KC; ++r) acc[u] ^= v[r];
+        } else {
           const uint64_t g = gidx(i + u);
           const uint8_t* par = RECOVER ? a.parity + (lane_on && g < a.n_groups ? g : 0) * a.parity_stride + off
                                        : nullptr;
-#pragma unroll
-          for (int r = 0; r < KC; ++r) {
-            const uint8_t* q = (RECOVER && (uint32_t)r == m[u]) ? par : src[u] + r * a.row_stride;
-            if constexpr (EDGE) {
-              // EDGE: windows in the first / last 128-B line of a row (lines
-              // the neighbouring row shares) by default-policy loads, so the
-              // second row's load finds the line in L2; nt loads elsewhere
-              const uint32_t aw = (uint32_t)(uintptr_t)q;
-              const uint32_t rs = (uint32_t)(uintptr_t)(src[u] - off + r * a.row_stride);
-              const bool edge = (aw >> 7) == (rs >> 7) || ((aw + 15u) >> 7) == ((rs + a.L - 1u) >> 7);
-              v[u][r] = edge ? ld16t<false>(q) : ld16t<true>(q);
-            } else {
-              v[u][r] = ld16t<NTLD>(q);
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < kPhU; ++u)
-#pragma unroll
-          for (int r = 0; r < KC; ++r) acc[u] ^= v[u][r];
-      } else {
-        // runtime k (> 16: every k up to 16 is templated): batches of up
-        // to RTB loads in flight, as even as possible (xor_rows_rt)
-#pragma unroll
-        for (int u = 0; u < kPhU; ++u) {
-          const uint64_t g = gidx(i + u);
-          const uint8_t* par = RECOVER ? a.parity + (lane_on && g < a.n_groups ? g : 0) * a.parity_stride + off
-                                       : nullptr;
-          xor_rows_rt<RTB, RECOVER, NTLD>(acc[u], src[u], a.row_stride, k, m[u], par);
+          xor_rows_rt<RTB, RECOVER, true>(acc[u], src[u], a.row_stride, k, m[u], par);
         }
       }
       if constexpr (RECOVER) {
-        if (i + kPhU < NL) {
+        if (i + U < NL) {
 #pragma unroll
-          for (int u = 0; u < kPhU; ++u) {
-            const uint64_t g = gidx(i + kPhU + u);
+          for (int u = 0; u < U; ++u) {
+            const uint64_t g = gidx(i + U + u);
             m_next[u] = lane_on && g < a.n_groups ? a.missing[g] : 0u;
           }
         }
       }
 #pragma unroll
-      for (int u = 0; u < kPhU; ++u) s_par[i + u][tid] = acc[u];
+      for (int u = 0; u < U; ++u) s_par[i + u][tid] = acc[u];
     }
     uint32_t ron[2] = {0u, 0u};  // step j's lane is on: bit j % 32 of word j / 32
     bool rbad = false;           // recover: a register step's lost slot out of range
     if constexpr (RS > 0) {
       // one live row address, advanced step by step (the compiler would
       // otherwise keep every step's address live across the unrolled steps)
-      const uint64_t g0r = gidx(STEPS);
+      const uint64_t g0r = gidx(kPhSteps);
       const uint8_t* q = a.rows + g0r * a.group_stride + off;
       const uint64_t dq = B * gpb * a.group_stride;
+      // (recover: qp, the step's parity address, is no longer loaded from --
+      // the parity rows are loaded before the steps -- but it is still
+      // advanced and fenced with q: the fences are kept exactly as measured)
       const uint8_t* qp = RECOVER ? a.parity + g0r * a.parity_stride + off : nullptr;
       const uint64_t dqp = RECOVER ? B * gpb * a.parity_stride : 0u;
-      if constexpr (RECOVER && RPF && !RPFE) {
-        // RPF: every register step's parity row first (one stream, as the
-        // LDS steps' PARFIRST), then the received rows step by step
+      if constexpr (RECOVER) {
+        // every register step's parity row first (one stream, as the LDS
+        // steps'), then the received rows step by step
 #pragma unroll
         for (int j = 0; j < RS; ++j) {
           const uint64_t g = g0r + (uint64_t)j * B * gpb;
-          const bool on = lane_on && g < a.n_groups && STEPS + j < SP;
-          racc[j] = ld16t<NTLD>(a.parity + (on ? g : 0) * a.parity_stride + off);
+          const bool on = lane_on && g < a.n_groups && kPhSteps + j < SP;
+          racc[j] = ld16t<true>(a.parity + (on ? g : 0) * a.parity_stride + off);
         }
       }
 #pragma unroll
       for (int j = 0; j < RS; ++j) {
         const uint64_t g = g0r + (uint64_t)j * B * gpb;
-        bool on = lane_on && g < a.n_groups && STEPS + j < SP;
+        bool on = lane_on && g < a.n_groups && kPhSteps + j < SP;
         u32x4 v[KC];
         if constexpr (RECOVER) {
           uint32_t mj = m_reg[j];
@@ -585,15 +558,14 @@ __global__ __launch_bounds__(NTHR) void phase_xor_kernel(FixedArgs a, uint32_t C
           }
           const uint8_t* qq = on ? q : a.rows + off;
           // the parity row, then the k-1 received rows in order (compact)
-          if constexpr (RPF) v[0] = racc[j];
-          else v[0] = ld16t<NTLD>(on ? qp : a.parity + off);
+          v[0] = racc[j];
 #pragma unroll
           for (int r = 0; r + 1 < KC; ++r)
-            v[r + 1] = ld16t<NTLD>(qq + ((uint32_t)r + ((uint32_t)r >= mj ? 1u : 0u)) * a.row_stride);
+            v[r + 1] = ld16t<true>(qq + ((uint32_t)r + ((uint32_t)r >= mj ? 1u : 0u)) * a.row_stride);
         } else {
           const uint8_t* qq = on ? q : a.rows + off;
 #pragma unroll
-          for (int r = 0; r < KC; ++r) v[r] = ld16t<NTLD>(qq + r * a.row_stride);
+          for (int r = 0; r < KC; ++r) v[r] = ld16t<true>(qq + r * a.row_stride);
         }
         ron[j / 32] |= on ? 1u << (j % 32) : 0u;
         u32x4 x = v[0];
@@ -613,7 +585,7 @@ __global__ __launch_bounds__(NTHR) void phase_xor_kernel(FixedArgs a, uint32_t C
     if constexpr (RECOVER) {
       if (((bad_lo | bad_hi) != 0u || rbad) && t == 0u) atomicOr(a.err, kErrMissingIndex);
     }
-    phase_meet(a.phase_sync, MEET2 ? 2u * p + 1u : p + 1u);
+    phase_meet(a.phase_sync, p + 1u);
     // INPL: the output row of group g is its own row missing[g] (the in-slot
     // recover written in place; every read of the phase is done by now, and
     // no other workgroup reads this group).  It runs at 0.73-0.76 of 8 TB/s
@@ -635,7 +607,7 @@ __global__ __launch_bounds__(NTHR) void phase_xor_kernel(FixedArgs a, uint32_t C
       }
     };
 #pragma unroll 4
-    for (int i = 0; i < STEPS; ++i) {
+    for (int i = 0; i < kPhSteps; ++i) {
       const uint64_t g = gidx(i);
       const uint32_t skip = RECOVER ? ((i < 32 ? bad_lo >> i : bad_hi >> (i - 32)) & 1u) : 0u;
       bool on = lane_on && g < a.n_groups && !skip && i < NL;
@@ -645,7 +617,7 @@ __global__ __launch_bounds__(NTHR) void phase_xor_kernel(FixedArgs a, uint32_t C
     if constexpr (RS > 0) {
 #pragma unroll
       for (int j = 0; j < RS; ++j) {
-        const uint64_t g = gidx(STEPS + j);
+        const uint64_t g = gidx(kPhSteps + j);
         bool on = ((ron[j / 32] >> (j % 32)) & 1u) != 0u;
         uint8_t* d = dst(on ? g : 0, on);
         if (on) st16t<true>(d, racc[j]);
@@ -654,7 +626,6 @@ __global__ __launch_bounds__(NTHR) void phase_xor_kernel(FixedArgs a, uint32_t C
     if constexpr (INPL) {
       if (ibad && t == 0u) atomicOr(a.err, kErrMissingIndex);
     }
-    if constexpr (MEET2) phase_meet(a.phase_sync, 2u * p + 2u);
   }
   phase_exit(a.phase_sync, a.phase_host);
 }
@@ -2442,8 +2413,8 @@ hipError_t launch_fixed_k(const FixedArgs& a, uint32_t C, uint32_t gpb, uint64_t
   return hipGetLastError();
 }
 
-// Register-held steps per phase for a templated group size (0: none): every
-// templated k takes kPhRegSteps (round 4; round 3 had
+// The group sizes with a templated phased body.  Every templated k takes
+// kPhRegSteps register-held steps per phase (round 4; round 3 had
 // them for k = 10 only; round 5 templates every k up to 16).  Larger k run
 // the runtime-k body with the LDS steps alone.
 // Round 6: the phased RECOVER of group sizes 17-25 is templated too (its
@@ -2459,9 +2430,6 @@ hipError_t launch_fixed_k(const FixedArgs& a, uint32_t C, uint32_t gpb, uint64_t
 __host__ __device__ constexpr bool phase_k_templated(bool recover, uint32_t k) {
   return (k >= 2u && k <= 16u) || (recover && k >= 17u && k <= 25u);
 }
-__host__ __device__ constexpr uint32_t phase_reg_steps(bool recover, uint32_t k) {
-  return phase_k_templated(recover, k) ? (uint32_t)kPhRegSteps : 0u;
-}
 
 // The runtime-k phased body's load batch (k > 16) by operation and group
 // size, from the round-6 per-k table (tools/phase_k_table.py, 2^20 groups up
@@ -2473,52 +2441,53 @@ __host__ __device__ constexpr uint32_t phase_rt_batch(bool recover, uint32_t k) 
   return recover && k <= 32u ? 32u : 16u;
 }
 
+// The body one phased launch gets.  The only place that decides it: phase_plan
+// sizes the phases by it and launch_phase_k launches it, so the phase count
+// cannot be computed for a phase length the launched body does not have.
+struct PhaseBody {
+  bool templated;      // KC = k; otherwise the runtime-k body, KC = 0
+  uint32_t reg_steps;  // RS: kPhRegSteps or 0 (templated k only)
+  uint32_t rt_batch;   // RTB: 16 or 32 (runtime k only)
+};
+PhaseBody phase_body(const FixedArgs& a) {
+  const bool inpl = a.inplace_missing != nullptr, recover = a.parity != nullptr && !inpl;
+  // (test hook rt_batch: the runtime-k body with that batch wherever k > 16,
+  // the A/B of tools/phase_k_table.py)
+  if (phase_k_templated(recover, a.k) && !(a.rt_batch != 0u && a.k > 16u))
+    // (test hook no_regsteps: the LDS steps alone; not for the in-place form)
+    return {true, a.no_regsteps != 0u && !inpl ? 0u : (uint32_t)kPhRegSteps, 32u};
+  return {false, 0u, (a.rt_batch ? a.rt_batch : phase_rt_batch(recover, a.k)) == 16u ? 16u : 32u};
+}
+
+template <int KC, bool RECOVER, int RS, bool INPL, int RTB>
+hipError_t launch_phase_body(const FixedArgs& a, uint32_t C, uint32_t gpb, uint32_t grid,
+                             uint32_t nphase, hipStream_t s) {
+  hipLaunchKernelGGL((phase_xor_kernel<KC, RECOVER, RS, INPL, RTB>), dim3(grid), dim3(kBlock), 0, s,
+                     a, C, gpb, nphase);
+  return hipGetLastError();
+}
+
 template <bool RECOVER, bool INPL = false>
-hipError_t launch_phase_k(const FixedArgs& a, uint32_t C, uint32_t gpb, uint32_t grid,
+hipError_t launch_phase_k(const FixedArgs& a, PhaseBody b, uint32_t C, uint32_t gpb, uint32_t grid,
                           uint32_t nphase, hipStream_t s) {
-  const bool rs = a.no_regsteps == 0u;
-  // (test hook rt_batch: the runtime-k body even where k is templated)
-  switch (a.rt_batch != 0u && a.k > 16u ? 0u : a.k) {
-    // templated k: kPhRegSteps more steps per phase held in registers after
-    // the LDS steps (recover: their parity rows first, RPF), or without them
-    // (test hook; not for the in-place form)
-#define QFEC_K_CASE(KV)                                                                        \
-  case KV:                                                                                      \
-    if (rs || INPL)                                                                             \
-      hipLaunchKernelGGL((phase_xor_kernel<KV, RECOVER, false, false, kPhUDefault, kPhSteps,    \
-                                           kBlock, false, true, true, false, true, kPhRegSteps, \
-                                           true, false, INPL>),                                 \
-                         dim3(grid), dim3(kBlock), 0, s, a, C, gpb, nphase);                    \
-    else                                                                                        \
-      hipLaunchKernelGGL((phase_xor_kernel<KV, RECOVER>), dim3(grid), dim3(kBlock), 0, s, a, C, \
-                         gpb, nphase);                                                          \
+#define QFEC_PHASE(KC_, RS_, INPL_, RTB_) \
+  launch_phase_body<KC_, RECOVER, RS_, INPL_, RTB_>(a, C, gpb, grid, nphase, s)
+  if (!b.templated)
+    return b.rt_batch == 16u ? QFEC_PHASE(0, 0, INPL, 16) : QFEC_PHASE(0, 0, INPL, 32);
+  // (the in-place form has no body without register steps)
+  if (INPL && b.reg_steps == 0u) return hipErrorInvalidValue;
+  switch (a.k) {
+#define QFEC_K_CASE(KV)                                                                          \
+  case KV:                                                                                       \
+    if constexpr (phase_k_templated(RECOVER, KV))                                                \
+      return b.reg_steps ? QFEC_PHASE(KV, kPhRegSteps, INPL, 32) : QFEC_PHASE(KV, 0, false, 32); \
     break;
     QFEC_K_ALL(QFEC_K_CASE)
-    default:
-      if constexpr (RECOVER) {
-        switch (a.rt_batch != 0u ? 0u : a.k) {
-          QFEC_K_PHASE_RECOVER(QFEC_K_CASE)
-          default:
-            break;
-        }
-        if (a.rt_batch == 0u && phase_k_templated(true, a.k)) break;
-      }
-      // runtime k: batches of up to 16 or 32 loads, by the measured table
-      // (phase_rt_batch; test hook rt_batch: either, the A/B of
-      // tools/phase_k_table.py)
-      if ((a.rt_batch ? a.rt_batch : phase_rt_batch(RECOVER, a.k)) == 16u)
-        hipLaunchKernelGGL((phase_xor_kernel<0, RECOVER, false, false, kPhUDefault, kPhSteps, kBlock,
-                                             false, true, true, false, true, 0, false, false, INPL,
-                                             16>),
-                           dim3(grid), dim3(kBlock), 0, s, a, C, gpb, nphase);
-      else
-        hipLaunchKernelGGL((phase_xor_kernel<0, RECOVER, false, false, kPhUDefault, kPhSteps, kBlock,
-                                             false, true, true, false, true, 0, false, false, INPL,
-                                             32>),
-                           dim3(grid), dim3(kBlock), 0, s, a, C, gpb, nphase);
-  }
+    QFEC_K_PHASE_RECOVER(QFEC_K_CASE)
 #undef QFEC_K_CASE
-  return hipGetLastError();
+  }
+#undef QFEC_PHASE
+  return hipErrorInvalidValue;  // no such instantiation: phase_body and the lists above disagree
 }
 
 // The phased kernel for a batch of at least kPhMinPhases phases (about 184K
@@ -2569,12 +2538,7 @@ bool phase_plan(const FixedArgs& a, uint32_t gpb, uint32_t* grid, uint32_t* npha
   const uint64_t per = (uint64_t)wg * kPhSteps * gpb;
   const uint64_t np = (a.n_groups + per - 1) / per;
   if (np < (a.phase_min ? a.phase_min : kPhMinPhases) || np > 0xFFFFFFFFull) return false;
-  const uint64_t per_l =
-      (uint64_t)wg *
-      (kPhSteps + ((a.no_regsteps && !a.inplace_missing) || (a.rt_batch != 0u && a.k > 16u)
-                       ? 0u
-                       : phase_reg_steps(a.parity != nullptr && !a.inplace_missing, a.k))) *
-      gpb;
+  const uint64_t per_l = (uint64_t)wg * (kPhSteps + phase_body(a).reg_steps) * gpb;
   *grid = wg;
   *nphase = (uint32_t)((a.n_groups + per_l - 1) / per_l);
   return true;
@@ -2585,6 +2549,20 @@ bool phase_plan(const FixedArgs& a, uint32_t gpb, uint32_t* grid, uint32_t* npha
 uint32_t phase_steps_for(const FixedArgs& a, uint32_t gpb, uint32_t grid, uint32_t nphase) {
   const uint64_t per_step = (uint64_t)grid * gpb * nphase;
   return (uint32_t)((a.n_groups + per_step - 1) / per_step);
+}
+
+// Groups [g, g + at most maxg) of a batch as a launch of their own.
+FixedArgs fixed_slice(const FixedArgs& a0, uint64_t g, uint64_t maxg) {
+  FixedArgs a = a0;
+  a.n_groups = std::min<uint64_t>(maxg, a0.n_groups - g);
+  a.rows = a0.rows + g * a0.group_stride;
+  if (a0.parity != nullptr) {
+    a.parity = a0.parity + g * a0.parity_stride;
+    a.missing = a0.missing + g;
+  }
+  a.out = a0.out + g * a0.out_stride;
+  if (a0.inplace_missing) a.inplace_missing = a0.inplace_missing + g;
+  return a;
 }
 
 }  // namespace
@@ -2603,15 +2581,7 @@ hipError_t launch_fixed(const FixedArgs& a0, bool nontemporal, hipStream_t s) {
   if (a0.L < 16u) {
     const uint64_t maxg = kMaxBlocks256 * kBlock / a0.L;  // one lane per output byte
     for (uint64_t g = 0; g < a0.n_groups; g += maxg) {
-      FixedArgs a = a0;
-      a.n_groups = std::min<uint64_t>(maxg, a0.n_groups - g);
-      a.rows = a0.rows + g * a0.group_stride;
-      if (recover) {
-        a.parity = a0.parity + g * a0.parity_stride;
-        a.missing = a0.missing + g;
-      }
-      a.out = a0.out + g * a0.out_stride;
-      if (a0.inplace_missing) a.inplace_missing = a0.inplace_missing + g;
+      const FixedArgs a = fixed_slice(a0, g, maxg);
       const uint64_t blocks = (a.n_groups * a.L + kBlock - 1) / kBlock;
       if (recover)
         hipLaunchKernelGGL(fixed_small_kernel<true>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, a);
@@ -2628,21 +2598,14 @@ hipError_t launch_fixed(const FixedArgs& a0, bool nontemporal, hipStream_t s) {
   if (a0.phase_sync && nontemporal && phase_plan(a0, gpb, &grid, &nphase)) {
     FixedArgs a = a0;
     a.phase_steps = phase_steps_for(a0, gpb, grid, nphase);
-    if (a.inplace_missing) return launch_phase_k<false, true>(a, C, gpb, grid, nphase, s);
-    return recover ? launch_phase_k<true>(a, C, gpb, grid, nphase, s)
-                   : launch_phase_k<false>(a, C, gpb, grid, nphase, s);
+    const PhaseBody b = phase_body(a);
+    if (a.inplace_missing) return launch_phase_k<false, true>(a, b, C, gpb, grid, nphase, s);
+    return recover ? launch_phase_k<true>(a, b, C, gpb, grid, nphase, s)
+                   : launch_phase_k<false>(a, b, C, gpb, grid, nphase, s);
   }
   const uint64_t maxg = kMaxBlocks256 * gpb;
   for (uint64_t g = 0; g < a0.n_groups; g += maxg) {
-    FixedArgs a = a0;
-    a.n_groups = std::min<uint64_t>(maxg, a0.n_groups - g);
-    a.rows = a0.rows + g * a0.group_stride;
-    if (recover) {
-      a.parity = a0.parity + g * a0.parity_stride;
-      a.missing = a0.missing + g;
-    }
-    a.out = a0.out + g * a0.out_stride;
-    if (a0.inplace_missing) a.inplace_missing = a0.inplace_missing + g;
+    const FixedArgs a = fixed_slice(a0, g, maxg);
     const uint64_t blocks = (a.n_groups + gpb - 1) / gpb;
     hipError_t e;
     if (a.inplace_missing)

@@ -283,27 +283,17 @@ int main(int argc, char** argv) {
     a.ncu = (uint32_t)ncu;
     CK(qfec::launch_fixed(a, true, 0));
   };
-  // the product's phase_xor_kernel instantiated directly: MEET2 x FLAT
+  // the product's phase_xor_kernel instantiated directly: the LDS steps alone
+  // and with RS more steps held in registers (recover: their parity rows first)
   using PK = void (*)(qfec::FixedArgs, uint32_t, uint32_t, uint32_t);
   std::vector<std::pair<std::string, PK>> pks = {
       {"prod (256 x 40)", qfec::phase_xor_kernel<10, false>},
       {"prod recover (256 x 40)", qfec::phase_xor_kernel<10, true>},
-      {"prod recover parity-first", qfec::phase_xor_kernel<10, true, false, false, 1, 40, 256, false, true>},
-      {"prod dflt-load", qfec::phase_xor_kernel<10, false, false, false, 1, 40, 256, false, true, false>},
-      {"prod recover dflt-load", qfec::phase_xor_kernel<10, true, false, false, 1, 40, 256, false, true, false>},
-      {"prod edge-dflt", qfec::phase_xor_kernel<10, false, false, false, 1, 40, 256, false, true, true, true>},
-      {"prod recover compact", qfec::phase_xor_kernel<10, true, false, false, 1, 40, 256, false, true, true, false, true>},
-      {"prod recover masked", qfec::phase_xor_kernel<10, true, false, false, 1, 40, 256, false, true, true, false, false>},
-      {"prod 256 x 40+32", qfec::phase_xor_kernel<10, false, false, false, 1, 40, 256, false, true, true, false, true, 32>},
-      {"prod recover 40+32", qfec::phase_xor_kernel<10, true, false, false, 1, 40, 256, false, true, true, false, true, 32>},
-      {"prod recover 40+32 rpf", qfec::phase_xor_kernel<10, true, false, false, 1, 40, 256, false, true, true, false, true, 32, true>},
-      {"prod recover 40+48 rpf", qfec::phase_xor_kernel<10, true, false, false, 1, 40, 256, false, true, true, false, true, 48, true>},
-      // round 4: recover with fewer / other register steps
-      {"prod recover 40+32 rpf early", qfec::phase_xor_kernel<10, true, false, false, 1, 40, 256, false, true, true, false, true, 32, true, true>},
-      {"prod recover 40+32 rpf again", qfec::phase_xor_kernel<10, true, false, false, 1, 40, 256, false, true, true, false, true, 32, true>},
-      {"prod recover 40+32 rpf early again", qfec::phase_xor_kernel<10, true, false, false, 1, 40, 256, false, true, true, false, true, 32, true, true>},
-      {"prod 256 x 40+56", qfec::phase_xor_kernel<10, false, false, false, 1, 40, 256, false, true, true, false, true, 56>},
-      {"prod 256 x 40+48", qfec::phase_xor_kernel<10, false, false, false, 1, 40, 256, false, true, true, false, true, 48>},
+      {"prod 256 x 40+32", qfec::phase_xor_kernel<10, false, 32>},
+      {"prod recover 40+32 rpf", qfec::phase_xor_kernel<10, true, 32>},
+      {"prod recover 40+48 rpf", qfec::phase_xor_kernel<10, true, 48>},
+      {"prod 256 x 40+56", qfec::phase_xor_kernel<10, false, 56>},
+      {"prod 256 x 40+48", qfec::phase_xor_kernel<10, false, 48>},
   };
   pks.push_back({"prod recover one-pass", nullptr});
   uint8_t* d_miss;
@@ -333,23 +323,13 @@ int main(int argc, char** argv) {
       a.missing = d_miss;
     }
     if (!pks[w].second) a.phase_sync = nullptr;
-    // geometry from the name: threads x steps, blocks per CU
-    uint32_t nt = 256, st = 40, bpc = 1;
-    if (pks[w].first.find("512 x 20") != std::string::npos) nt = 512, st = 20;
-    if (pks[w].first.find("1024 x 10") != std::string::npos) nt = 1024, st = 10;
-    if (pks[w].first.find("256 x 20") != std::string::npos) st = 20, bpc = 2;
-    if (pks[w].first.find("256 x 32") != std::string::npos) st = 32;
-    if (pks[w].first.find("128 x 80") != std::string::npos) nt = 128, st = 80;
-    if (pks[w].first.find("192 x 53") != std::string::npos) nt = 192, st = 53;
+    // steps per phase from the name: the 40 LDS steps + the register steps
+    const uint32_t nt = 256;
+    uint32_t st = 40;
     if (pks[w].first.find("40+32") != std::string::npos) st = 72;
-    if (pks[w].first.find("40+56") != std::string::npos) st = 96;
-    if (pks[w].first.find("40+40") != std::string::npos) st = 80;
     if (pks[w].first.find("40+48") != std::string::npos) st = 88;
-    if (pks[w].first.find("40+64") != std::string::npos) st = 104;
-    if (pks[w].first.find("40+24") != std::string::npos) st = 64;
-    if (pks[w].first.find("40+16") != std::string::npos) st = 56;
-    if (pks[w].first.find("32+32") != std::string::npos) st = 64;
-    const uint32_t gpb = nt / 85u, grid = ncu * bpc;
+    if (pks[w].first.find("40+56") != std::string::npos) st = 96;
+    const uint32_t gpb = nt / 85u, grid = ncu;
     const uint64_t per = (uint64_t)grid * st * gpb;
     const uint32_t nph = (uint32_t)((G + per - 1) / per);
     (void)pnph;
