@@ -236,6 +236,77 @@ int qfec_recover_inslot_batch_strided(qfec_ctx* ctx, uint8_t* rows, const uint8_
                                       uint64_t group_stride, uint64_t n_groups, uint8_t* out,
                                       uint64_t out_stride, uint32_t flags);
 
+/* ---- revive from receive maps ------------------------------------------- */
+/* The receiver's decision and the revive in one call, for a batch that stays
+ * on the device: which groups are finished, which lost exactly one protected
+ * packet and hold their FEC packet (those are rebuilt), which are beyond
+ * repair.  Replaces QuicFecGroup::NumMissingPackets() + IsFinished() +
+ * CanRevive() + Revive() over a batch of groups, at the receive hook
+ * QuicConnection::ProcessValidatedPacket
+ * (src/net/quic/core/quic_connection.cc:1388-1392); the recover calls above
+ * take that decision as an input (missing_idx) and read every group.
+ *
+ * received: one receive map per group, map_stride bytes apart
+ *   (map_stride >= ceil((k + 1) / 8); the dense form uses exactly that).  Bit i
+ *   of a map is (map[i / 8] >> (i % 8)) & 1: bits 0 .. k-1 say whether data
+ *   packet i arrived, bit k whether the FEC packet arrived; bits above k in
+ *   the last byte are ignored.  rows / parity: as qfec_recover_batch.
+ * With miss = k - popcount(data bits):
+ *   miss == 0                      QFEC_GROUP_COMPLETE, whatever the FEC bit
+ *   miss == 1 and the FEC bit set  QFEC_GROUP_REVIVED, m = the clear data bit
+ *   anything else                  QFEC_GROUP_UNREVIVABLE
+ * An unrevivable group is a result, not an error (as an invalid ack is for
+ * qfec_entropy_validate_batch).
+ *
+ * Outputs (status is required, every other one may be NULL):
+ *   status[g]        one of the three codes
+ *   revived_idx[g]   m for revived groups, 0xFF otherwise
+ *   out != NULL:     out + g*out_stride receives the L revived bytes of revived
+ *                    groups only, parity[g] XOR_{i != m} rows[g][i]; the out
+ *                    rows of other groups are not written
+ *   out == NULL:     in place, rows[g][m] receives the revived packet; no other
+ *                    byte of rows is written
+ *   revived_list     room for n_groups entries: the indices of the revived
+ *                    groups in ascending order (what the framer walks for the
+ *                    ack's revived packets); entries from the count on are not
+ *                    written
+ *   counts[0..2]     groups per status; counts[1] is the length of the list
+ * Reads: the slot of a missing packet and the parity row of a group without
+ * its FEC packet are never read; rows and parity of complete and unrevivable
+ * groups are not read at all -- a batch with 5% of its groups to revive moves
+ * about 5% of the dense recover's bytes plus the maps.
+ *
+ * Device pointers only (QFEC_PTR_HOST, QFEC_PTR_MAPPED and QFEC_ASYNC are
+ * refused); QFEC_CACHED as for the fixed-shape calls.  The call queues its
+ * kernels on the context's stream and returns: it never waits for the device
+ * and never reads the revived count back; results are valid after qfec_sync.
+ * Its intermediate state (per-workgroup counts, the packed list of revivable
+ * groups) lives in context-owned device scratch, grown on demand (an
+ * outgrown block is released by the next qfec_sync, so growing does not wait
+ * either) and freed by qfec_destroy.
+ * Limits and codes as qfec_recover_batch_strided (1 <= k <= 255,
+ * 1 <= L <= 1452, strides >= L, else -QUIC_INVALID_FEC_DATA), and the same
+ * code for a map_stride below ceil((k + 1) / 8); a NULL rows, parity (even if
+ * no group would read it), received or status and the refused pointer flags
+ * return QFEC_ERR_INTERNAL.  A refused call launches nothing and writes
+ * nothing.  n_groups == 0 succeeds (counts, if given, receives three
+ * zeroes) and, as for qfec_recover_batch, is decided before the buffers are
+ * looked at: NULL buffers pass with it. */
+#define QFEC_GROUP_COMPLETE 0u    /* every data packet arrived (IsFinished): nothing to do */
+#define QFEC_GROUP_REVIVED 1u     /* one data packet missing, FEC packet present (CanRevive): rebuilt */
+#define QFEC_GROUP_UNREVIVABLE 2u /* two or more data packets missing, or one missing and no FEC packet */
+int qfec_revive_batch(qfec_ctx* ctx, uint8_t* rows, const uint8_t* parity, const uint8_t* received,
+                      uint32_t k, uint32_t L, uint64_t n_groups, uint8_t* out, uint8_t* status,
+                      uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
+                      uint32_t flags);
+int qfec_revive_batch_strided(qfec_ctx* ctx, uint8_t* rows, const uint8_t* parity,
+                              const uint8_t* received, uint32_t k, uint32_t L,
+                              uint64_t row_stride, uint64_t group_stride,
+                              uint64_t parity_stride, uint64_t map_stride, uint64_t n_groups,
+                              uint8_t* out, uint64_t out_stride, uint8_t* status,
+                              uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
+                              uint32_t flags);
+
 /* ---- ragged batches (CSR) ---------------------------------------------- */
 /* Group g holds packets p in [grp_ptr[g], grp_ptr[g+1]) (1..255 of them);
  * packet p is pkt_len[p] (1..1452) bytes at bytes + pkt_off[p].

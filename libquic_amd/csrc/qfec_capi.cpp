@@ -164,6 +164,18 @@ struct qfec_ctx {
   // grow-only buffers kept for the context's life (no allocation per call)
   std::vector<void*> scratch_p;
   std::vector<size_t> scratch_n;
+  // device scratch of qfec_revive_batch (tile counts and offsets, totals,
+  // work list: qfec_internal.h ReviveArgs), grown on demand.  The call only
+  // queues work, so a call on another stream than the last one's first waits
+  // for revive_done (recorded after each call's launches, like phase_done).
+  void* d_revive = nullptr;
+  size_t revive_bytes = 0;
+  // blocks outgrown by a later call: queued work may still use them, and the
+  // call never waits, so they are freed by qfec_sync / qfec_destroy
+  std::vector<void*> revive_retired;
+  hipEvent_t revive_done = nullptr;
+  hipStream_t revive_stream = nullptr;
+  bool revive_recorded = false;
 };
 
 namespace {
@@ -1228,6 +1240,9 @@ void qfec_destroy(qfec_ctx* ctx) {
   }
   if (ctx->d_done) (void)hipFree(ctx->d_done);
   if (ctx->d_phase) (void)hipFree(ctx->d_phase);
+  if (ctx->d_revive) (void)hipFree(ctx->d_revive);
+  for (void* q : ctx->revive_retired) (void)hipFree(q);
+  if (ctx->revive_done) (void)hipEventDestroy(ctx->revive_done);
   for (void* q : ctx->scratch_p)
     if (q) (void)hipFree(q);
   if (ctx->h_flag) (void)hipHostFree(ctx->h_flag);
@@ -1252,7 +1267,15 @@ void* qfec_own_stream(qfec_ctx* ctx) { return ctx ? (void*)ctx->own_stream : nul
 int qfec_sync(qfec_ctx* ctx) {
   int rc = bind(ctx);
   if (rc) return rc;
-  return collect_error(ctx, ctx->stream);
+  rc = collect_error(ctx, ctx->stream);
+  // revive scratch outgrown since the last sync: the stream has drained (and
+  // so has a revive queued on another stream before qfec_set_stream)
+  if (!ctx->revive_retired.empty()) {
+    if (ctx->revive_recorded) (void)hipEventSynchronize(ctx->revive_done);
+    for (void* q : ctx->revive_retired) (void)hipFree(q);
+    ctx->revive_retired.clear();
+  }
+  return rc;
 }
 
 int qfec_complete(qfec_ctx* ctx, int wait) {
@@ -1400,6 +1423,87 @@ int qfec_recover_inslot_batch(qfec_ctx* ctx, uint8_t* rows, const uint8_t* missi
                               uint32_t L, uint64_t n_groups, uint8_t* out, uint32_t flags) {
   return qfec_recover_inslot_batch_strided(ctx, rows, missing_idx, k, L, L, (uint64_t)k * L,
                                            n_groups, out, L, flags);
+}
+
+// Revive from per-group receive maps: the receiver half of QuicFecGroup
+// (NumMissingPackets / CanRevive / IsFinished + Revive) for a device-resident
+// batch.  The call only queues kernels on the context's stream: the revived
+// count is never read back and nothing here waits for the device: a call that
+// has to grow the scratch allocates the larger block and leaves the old one,
+// which queued work may still use, to qfec_sync.
+int qfec_revive_batch_strided(qfec_ctx* ctx, uint8_t* rows, const uint8_t* parity,
+                              const uint8_t* received, uint32_t k, uint32_t L,
+                              uint64_t row_stride, uint64_t group_stride,
+                              uint64_t parity_stride, uint64_t map_stride, uint64_t n_groups,
+                              uint8_t* out, uint64_t out_stride, uint8_t* status,
+                              uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
+                              uint32_t flags) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_fixed(ctx, k, L, row_stride, group_stride, parity_stride, out ? out_stride : L)))
+    return rc;
+  if (map_stride < (uint64_t)k / 8u + 1u)
+    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+                "receive map stride %llu smaller than the %u bytes of %u + 1 bits",
+                (unsigned long long)map_stride, k / 8u + 1u, k);
+  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "revive from receive maps: device pointers only, queued on the context's stream "
+                "(QFEC_PTR_HOST, QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)");
+  if (n_groups == 0) {
+    if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(uint64_t), ctx->stream));
+    return QFEC_OK;
+  }
+  if (!rows || !parity || !received || !status) return fail(ctx, QFEC_ERR_INTERNAL, "null buffer");
+  if (n_groups >= (1ull << 56))
+    return fail(ctx, QFEC_ERR_INTERNAL, "more than 2^56 groups");
+  const uint64_t need = qfec::revive_scratch_bytes(n_groups);
+  if (ctx->revive_bytes < need) {
+    // the outgrown block is retired, not freed: hipFree would wait for the device
+    const size_t want = std::max<size_t>({(size_t)need, 2 * ctx->revive_bytes, 4096});
+    void* grown = nullptr;
+    QFEC_HIP(ctx, hipMalloc(&grown, want));
+    if (ctx->d_revive) ctx->revive_retired.push_back(ctx->d_revive);
+    ctx->d_revive = grown;
+    ctx->revive_bytes = want;
+  }
+  if (!ctx->revive_done)
+    QFEC_HIP(ctx, hipEventCreateWithFlags(&ctx->revive_done, hipEventDisableTiming));
+  if (ctx->revive_recorded && ctx->revive_stream != ctx->stream)
+    QFEC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->revive_done, 0));
+  qfec::ReviveArgs a{};
+  a.rows = rows;
+  a.parity = parity;
+  a.received = received;
+  a.out = out;
+  a.row_stride = row_stride;
+  a.group_stride = group_stride;
+  a.parity_stride = parity_stride;
+  a.map_stride = map_stride;
+  a.out_stride = out_stride;
+  a.n_groups = n_groups;
+  a.k = k;
+  a.L = L;
+  a.status = status;
+  a.revived_idx = revived_idx;
+  a.revived_list = revived_list;
+  a.counts = counts;
+  a.ncu = ctx->ncu;
+  qfec::revive_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_revive(a, (flags & QFEC_CACHED) == 0, ctx->stream));
+  QFEC_HIP(ctx, hipEventRecord(ctx->revive_done, ctx->stream));
+  ctx->revive_stream = ctx->stream;
+  ctx->revive_recorded = true;
+  return QFEC_OK;
+}
+
+int qfec_revive_batch(qfec_ctx* ctx, uint8_t* rows, const uint8_t* parity, const uint8_t* received,
+                      uint32_t k, uint32_t L, uint64_t n_groups, uint8_t* out, uint8_t* status,
+                      uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
+                      uint32_t flags) {
+  return qfec_revive_batch_strided(ctx, rows, parity, received, k, L, L, (uint64_t)k * L, L,
+                                   (uint64_t)k / 8u + 1u, n_groups, out, L, status, revived_idx,
+                                   revived_list, counts, flags);
 }
 
 // ---- ragged ---------------------------------------------------------------

@@ -66,6 +66,56 @@ struct FixedArgs {
   const uint8_t* inplace_missing = nullptr;
 };
 
+// Revive from per-group receive maps (qfec_revive_batch; layout as
+// include/qfec.h).  The scratch pointers are context-owned device memory laid
+// out by revive_scratch_bytes: nothing of a call's intermediate state (the
+// revived count included) ever reaches the host.
+constexpr uint32_t kReviveTile = 256;    // groups per classify workgroup (one lane each)
+constexpr uint32_t kReviveListPad = 8;   // work-list entries readable past the revived count
+struct ReviveArgs {
+  uint8_t* rows;
+  const uint8_t* parity;
+  const uint8_t* received;
+  uint8_t* out;  // nullptr: in place, rows[g][m] receives the revived packet
+  uint64_t row_stride;
+  uint64_t group_stride;
+  uint64_t parity_stride;
+  uint64_t map_stride;
+  uint64_t out_stride;
+  uint64_t n_groups;
+  uint32_t k;
+  uint32_t L;
+  uint8_t* status;
+  uint8_t* revived_idx;    // nullable
+  uint64_t* revived_list;  // nullable
+  uint64_t* counts;        // nullable: [complete, revived, unrevivable]
+  // scratch: per classify tile its packed counts (revived | complete << 16)
+  // and the revived groups before it; the three totals; the work list, entry
+  // i = g << 8 | m of the i-th revived group, n_groups + kReviveListPad long
+  uint32_t* tile_cnt;
+  uint64_t* tile_off;
+  uint64_t* totals;
+  uint64_t* work;
+  uint32_t ncu;  // the device's CU count (sizes the revive grid)
+};
+inline uint64_t revive_tiles(uint64_t n_groups) {
+  return (n_groups + kReviveTile - 1) / kReviveTile;
+}
+// Bytes of scratch for n_groups, and the four pointers into a block of them.
+inline uint64_t revive_scratch_bytes(uint64_t n_groups) {
+  return 32 + (n_groups + kReviveListPad) * 8 + revive_tiles(n_groups) * 12;
+}
+inline void revive_scratch_layout(ReviveArgs& a, void* block) {
+  uint8_t* p = static_cast<uint8_t*>(block);
+  a.totals = reinterpret_cast<uint64_t*>(p);
+  a.work = reinterpret_cast<uint64_t*>(p + 32);
+  a.tile_off = a.work + a.n_groups + kReviveListPad;
+  a.tile_cnt = reinterpret_cast<uint32_t*>(a.tile_off + revive_tiles(a.n_groups));
+}
+// Four launches on s (classify, scan, emit, revive), ordered by the stream
+// alone.  n_groups > 0.
+hipError_t launch_revive(const ReviveArgs& a, bool nontemporal, hipStream_t s);
+
 // True if launch_fixed(a, nontemporal, ...) runs the phased kernel; *grid
 // (nullable): its workgroup count.
 bool fixed_uses_phases(const FixedArgs& a, bool nontemporal, uint32_t* grid = nullptr);

@@ -26,6 +26,9 @@
 //    phase_xor_kernel instead: the same lanes and loads in a persistent
 //    one-workgroup-per-CU grid that separates the row reads and the parity
 //    writes into grid-wide phases (0.80 of 8 TB/s on any buffer placement).
+//  * Revive from receive maps (qfec_revive_batch): classify / scan / emit build
+//    a packed list of the revivable groups on the device, and the recover
+//    body above runs over that list only (revive_xor_kernel).
 //  * Ragged CSR batches: eight groups per 4-wave block in one flat window
 //    space (ragged_block_kernel; the one-group body below is its exact
 //    fallback; the round-1/2 forms, one and two groups per wave, live in
@@ -662,6 +665,246 @@ __global__ __launch_bounds__(kBlock) void fixed_small_kernel(FixedArgs a) {
     return;
   }
   a.out[g * a.out_stride + j] = acc;
+}
+
+// ---------------------------------------------------------------------------
+// Revive from per-group receive maps (qfec_revive_batch).
+// ---------------------------------------------------------------------------
+// A batch in which most groups need nothing: classify every group from its
+// receive map (k + 1 bits), then run the recover body over a packed work list
+// of the revivable groups only, so the HBM traffic is that of the revived
+// groups plus the maps.  Four kernels on the stream, ordered by the kernel
+// boundaries alone -- no workgroup ever waits on another:
+//   classify : one lane per group, status / revived_idx out, each tile of 256
+//              groups leaves its revived and complete counts (ballots) in
+//              scratch;
+//   scan     : one workgroup, an exclusive scan over the tile counts: every
+//              tile's position in the work list, and the three totals;
+//   emit     : the classification again (the maps are 2 B per group at
+//              k = 10), every revived group's (g, m) into the work list and g
+//              into revived_list at its scanned position: ascending, no sort;
+//   revive   : fixed_xor_kernel's recover body with g and m from work-list
+//              entry i, a grid-stride loop over the list whose length the
+//              kernel reads from scratch (the host never learns it).
+constexpr uint32_t kGroupComplete = 0, kGroupRevived = 1, kGroupUnrevivable = 2;
+constexpr int kRvScanBlock = 1024;
+
+// Status of the group whose map starts at mp; m: its one clear data bit
+// (revived groups only, else 0xFF).  All shifts are 32-bit (the gfx950 64-bit
+// shift hazard).
+__device__ __forceinline__ uint32_t revive_classify(const uint8_t* mp, uint32_t k, uint32_t& m) {
+  uint32_t miss, first, fec;
+  if (k < 64u) {
+    // k + 1 <= 64 bits: the map as two 32-bit words
+    const uint32_t nb = k / 8u + 1u;
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; ++j) {
+      const uint32_t b = j < nb ? (uint32_t)mp[j] : 0u;
+      if (j < 4u) lo |= b << (8u * j);
+      else hi |= b << (8u * (j - 4u));
+    }
+    const uint32_t lom = k >= 32u ? 0xFFFFFFFFu : (1u << k) - 1u;
+    const uint32_t him = k > 32u ? (1u << (k - 32u)) - 1u : 0u;
+    const uint32_t zl = ~lo & lom, zh = ~hi & him;
+    miss = __popc(zl) + __popc(zh);
+    first = zl ? (uint32_t)__builtin_ctz(zl) : 32u + (zh ? (uint32_t)__builtin_ctz(zh) : 0u);
+    fec = k < 32u ? (lo >> k) & 1u : (hi >> (k - 32u)) & 1u;
+  } else {
+    miss = 0;
+    first = 0;
+    const uint32_t nfull = k / 8u, rem = k % 8u;
+    for (uint32_t b = 0; b < nfull; ++b) {
+      const uint32_t z = ~(uint32_t)mp[b] & 0xFFu;
+      if (z != 0u && miss == 0u) first = 8u * b + (uint32_t)__builtin_ctz(z);
+      miss += __popc(z);
+    }
+    const uint32_t last = mp[nfull];
+    const uint32_t z = ~last & ((1u << rem) - 1u);
+    if (z != 0u && miss == 0u) first = 8u * nfull + (uint32_t)__builtin_ctz(z);
+    miss += __popc(z);
+    fec = (last >> rem) & 1u;
+  }
+  m = 0xFFu;
+  if (miss == 0u) return kGroupComplete;
+  if (miss == 1u && fec != 0u) {
+    m = first;
+    return kGroupRevived;
+  }
+  return kGroupUnrevivable;
+}
+
+// EMIT = false: status, revived_idx and the tile's counts.  EMIT = true: the
+// work list and revived_list, at tile_off[tile] + the group's rank among the
+// tile's revived groups (wave ballots, the waves' counts through LDS).
+template <bool EMIT>
+__global__ __launch_bounds__(kReviveTile) void revive_classify_kernel(ReviveArgs a) {
+  __shared__ uint32_t s_w[kReviveTile / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const uint64_t g = tile * kReviveTile + tid;
+    uint32_t st = 3u, m = 0xFFu;  // 3: past the batch
+    if (g < a.n_groups) st = revive_classify(a.received + g * a.map_stride, a.k, m);
+    const uint64_t brev = __ballot(st == kGroupRevived);
+    if constexpr (!EMIT) {
+      const uint64_t bcomp = __ballot(st == kGroupComplete);
+      if (g < a.n_groups) {
+        a.status[g] = (uint8_t)st;
+        if (a.revived_idx) a.revived_idx[g] = (uint8_t)m;
+      }
+      if (lane == 0u) s_w[wave] = (uint32_t)__popcll(brev) | ((uint32_t)__popcll(bcomp) << 16);
+      __syncthreads();
+      if (tid == 0u) a.tile_cnt[tile] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    } else {
+      if (lane == 0u) s_w[wave] = (uint32_t)__popcll(brev);
+      __syncthreads();
+      if (st == kGroupRevived) {
+        uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(brev >> 32),
+                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)brev, 0u));
+        for (uint32_t w = 0; w < wave; ++w) rank += s_w[w];
+        const uint64_t pos = a.tile_off[tile] + rank;
+        a.work[pos] = (g << 8) | m;
+        if (a.revived_list) a.revived_list[pos] = g;
+      }
+    }
+    __syncthreads();  // s_w is reused by the next tile
+  }
+}
+static_assert(kReviveTile == 256, "four waves' counts are summed by hand above");
+
+// One workgroup: tile_off[i] = revived groups in tiles before i, then the
+// totals.  A tile of the scan is kRvScanBlock counts; the running bases are
+// uniform registers.
+__global__ __launch_bounds__(kRvScanBlock) void revive_scan_kernel(ReviveArgs a) {
+  __shared__ uint32_t s_rev[kRvScanBlock / 64], s_comp[kRvScanBlock / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
+  uint64_t base_rev = 0, base_comp = 0;
+  for (uint64_t t0 = 0; t0 < ntile; t0 += kRvScanBlock) {
+    const uint64_t i = t0 + tid;
+    const uint32_t c = i < ntile ? a.tile_cnt[i] : 0u;
+    const uint32_t rev = c & 0xFFFFu, comp = c >> 16;
+    uint32_t xr = rev, xc = comp;  // inclusive scans within the wave
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t yr = __shfl_up(xr, d), yc = __shfl_up(xc, d);
+      if (lane >= d) {
+        xr += yr;
+        xc += yc;
+      }
+    }
+    if (lane == 63u) {
+      s_rev[wave] = xr;
+      s_comp[wave] = xc;
+    }
+    __syncthreads();
+    uint32_t before = 0, tot_rev = 0, tot_comp = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kRvScanBlock / 64; ++w) {
+      if (w < wave) before += s_rev[w];
+      tot_rev += s_rev[w];
+      tot_comp += s_comp[w];
+    }
+    if (i < ntile) a.tile_off[i] = base_rev + before + (xr - rev);
+    base_rev += tot_rev;
+    base_comp += tot_comp;
+    __syncthreads();
+  }
+  if (tid == 0u) {
+    const uint64_t unrev = a.n_groups - base_rev - base_comp;
+    a.totals[kGroupComplete] = base_comp;
+    a.totals[kGroupRevived] = base_rev;
+    a.totals[kGroupUnrevivable] = unrev;
+    if (a.counts) {
+      a.counts[kGroupComplete] = base_comp;
+      a.counts[kGroupRevived] = base_rev;
+      a.counts[kGroupUnrevivable] = unrev;
+    }
+  }
+}
+
+// The recover body over the work list, L >= 16: lanes, windows and loads as
+// fixed_xor_kernel; workgroup step i takes entries [i * gpb, (i + 1) * gpb).
+// `work` and `totals` are separate restrict parameters so that their loads
+// stay SCALAR in the loop although the loop stores: every row address depends
+// on the entry, and a per-lane load of it would put a vector-memory round trip
+// in front of all of them (fixed_xor_kernel's SM path, -7% measured there).
+// SM (gpb <= 8): the workgroup's entries are eight uniform loads (the list is
+// readable kReviveListPad entries past the count) and a select by the lane's
+// group; smaller packets load their entry per lane.  (A template switch, not
+// a branch: with both forms in one loop the compiler waits for every vector
+// access, the previous step's store included, before a step's first load.)
+// In place (out == nullptr) the result goes to row m of the group's own rows:
+// the recover form never reads row m, and the clamped last window
+// min(t * 16, L - 16) stays inside row m, so no lane overwrites a byte another
+// lane still reads and, unlike the in-slot INPL body, no barrier is needed.
+template <int KC, bool NT, bool SM>
+__global__ __launch_bounds__(kBlock) void revive_xor_kernel(ReviveArgs a,
+                                                            const uint64_t* __restrict__ work,
+                                                            const uint64_t* __restrict__ totals,
+                                                            uint32_t C, uint32_t gpb) {
+  static_assert(kReviveListPad >= 8, "eight entries are loaded unconditionally");
+  const uint32_t tid = threadIdx.x;
+  const uint32_t gl = tid / C;  // entry within the workgroup's step
+  const uint32_t t = tid - gl * C;
+  const uint32_t off = min(t * 16u, a.L - 16u);
+  const uint32_t k = KC > 0 ? (uint32_t)KC : a.k;
+  const uint64_t count = totals[kGroupRevived];
+  const uint64_t nstep = (count + gpb - 1) / gpb;
+  for (uint64_t i = blockIdx.x; i < nstep; i += gridDim.x) {
+    const uint64_t eb = i * gpb;
+    uint64_t e;
+    if constexpr (SM) {
+      uint64_t w[8];
+#pragma unroll
+      for (uint32_t j = 0; j < 8u; ++j) w[j] = work[eb + j];
+      e = w[0];
+#pragma unroll
+      for (uint32_t j = 1; j < 8u; ++j) e = gl == j ? w[j] : e;
+    } else {
+      e = gl < gpb && eb + gl < count ? work[eb + gl] : 0ull;
+    }
+    if (gl >= gpb || eb + gl >= count) continue;
+    const uint64_t g = e >> 8;
+    const uint32_t m = (uint32_t)e & 0xFFu;
+    const uint8_t* src = a.rows + g * a.group_stride + off;
+    const uint8_t* par = a.parity + g * a.parity_stride + off;
+    u32x4 acc = {0u, 0u, 0u, 0u};
+    if constexpr (KC > 0) {
+#pragma unroll
+      for (uint32_t r = 0; r < (uint32_t)KC; ++r) {
+        const uint8_t* p = (r == m) ? par : src + r * a.row_stride;
+        acc ^= ld16t<NT>(p);
+      }
+    } else {
+      xor_rows_rt<8, true, NT>(acc, src, a.row_stride, k, m, par);
+    }
+    uint8_t* dst = a.out ? a.out + g * a.out_stride + off
+                         : const_cast<uint8_t*>(src) + (uint64_t)m * a.row_stride;
+    st16t<NT>(dst, acc);
+  }
+}
+
+// L < 16: one lane per revived byte, as fixed_small_kernel.
+__global__ __launch_bounds__(kBlock) void revive_small_kernel(ReviveArgs a,
+                                                              const uint64_t* __restrict__ work,
+                                                              const uint64_t* __restrict__ totals) {
+  const uint64_t nbyte = totals[kGroupRevived] * a.L;
+  for (uint64_t x = (uint64_t)blockIdx.x * kBlock + threadIdx.x; x < nbyte;
+       x += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t i = x / a.L;
+    const uint32_t j = (uint32_t)(x - i * a.L);
+    const uint64_t e = work[i];
+    const uint64_t g = e >> 8;
+    const uint32_t m = (uint32_t)e & 0xFFu;
+    uint8_t* src = a.rows + g * a.group_stride + j;
+    uint8_t acc = a.parity[g * a.parity_stride + j];
+    for (uint32_t r = 0; r < a.k; ++r)
+      if (r != m) acc ^= src[r * a.row_stride];
+    if (a.out) a.out[g * a.out_stride + j] = acc;
+    else src[(uint64_t)m * a.row_stride] = acc;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -2622,6 +2865,59 @@ hipError_t launch_fixed(const FixedArgs& a0, bool nontemporal, hipStream_t s) {
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+namespace {
+
+template <bool NT, bool SM>
+hipError_t launch_revive_k(const ReviveArgs& a, uint32_t C, uint32_t gpb, uint32_t grid,
+                           hipStream_t s) {
+  switch (a.k) {
+#define QFEC_K_CASE(KV)                                                                      \
+  case KV:                                                                                    \
+    hipLaunchKernelGGL((revive_xor_kernel<KV, NT, SM>), dim3(grid), dim3(kBlock), 0, s, a,    \
+                       a.work, a.totals, C, gpb);                                             \
+    break;
+    QFEC_K_ALL(QFEC_K_CASE)
+#undef QFEC_K_CASE
+    default:
+      hipLaunchKernelGGL((revive_xor_kernel<0, NT, SM>), dim3(grid), dim3(kBlock), 0, s, a,
+                         a.work, a.totals, C, gpb);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_revive(const ReviveArgs& a, bool nontemporal, hipStream_t s) {
+  if (a.n_groups == 0) return hipSuccess;
+  // classify and emit: grid-stride over the tiles of kReviveTile groups
+  const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
+  hipLaunchKernelGGL(revive_classify_kernel<false>, dim3(cgrid), dim3(kReviveTile), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(revive_scan_kernel, dim3(1), dim3(kRvScanBlock), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(revive_classify_kernel<true>, dim3(cgrid), dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  // revive: the count stays on the device, so the grid is sized by the device
+  // (eight workgroups per CU: every wave slot at up to 64 VGPRs) and by the
+  // worst case, whichever is smaller; workgroups loop over the list
+  const uint64_t resident = (uint64_t)(a.ncu ? a.ncu : 256u) * 8u;
+  if (a.L < 16u) {
+    const uint64_t blocks = (a.n_groups * a.L + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(revive_small_kernel, dim3((uint32_t)std::min(blocks, resident)),
+                       dim3(kBlock), 0, s, a, a.work, a.totals);
+    return hipGetLastError();
+  }
+  const uint32_t C = (a.L + 15u) / 16u;
+  const uint32_t gpb = kBlock / C;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((a.n_groups + gpb - 1) / gpb, resident);
+  if (gpb <= 8u)
+    return nontemporal ? launch_revive_k<true, true>(a, C, gpb, grid, s)
+                       : launch_revive_k<false, true>(a, C, gpb, grid, s);
+  return nontemporal ? launch_revive_k<true, false>(a, C, gpb, grid, s)
+                     : launch_revive_k<false, false>(a, C, gpb, grid, s);
 }
 
 constexpr int kRaggedBlockWaves = 4, kRaggedBlockGroups = 8;  // ragged_block_kernel shape

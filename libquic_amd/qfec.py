@@ -30,6 +30,9 @@ QFEC_ASYNC = 16
 QFEC_SCRATCH_OUTPUT = 32
 QFEC_SMALL_GROUPS = 64
 QFEC_PENDING = 1
+GROUP_COMPLETE = 0
+GROUP_REVIVED = 1
+GROUP_UNREVIVABLE = 2
 MAX_PACKET_SIZE = 1452
 DEFAULT_MAX_PACKET_SIZE = 1350
 MAX_GROUP_PACKETS = 255
@@ -65,6 +68,12 @@ SIGNATURES = [
     ("qfec_recover_inslot_batch_strided", C.c_int,
      [_vp, _u8p, _u8p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _u8p,
       C.c_uint64, C.c_uint32]),
+    ("qfec_revive_batch", C.c_int,
+     [_vp, _u8p, _u8p, _u8p, C.c_uint32, C.c_uint32, C.c_uint64, _u8p, _u8p, _u8p, _vp, _vp,
+      C.c_uint32]),
+    ("qfec_revive_batch_strided", C.c_int,
+     [_vp, _u8p, _u8p, _u8p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
+      C.c_uint64, C.c_uint64, _u8p, C.c_uint64, _u8p, _u8p, _vp, _vp, C.c_uint32]),
     ("qfec_encode_ragged", C.c_int,
      [_vp, _u8p, _vp, _vp, _vp, C.c_uint64, _u8p, _vp, _vp, C.c_uint32]),
     ("qfec_recover_ragged", C.c_int,
@@ -159,6 +168,20 @@ def load(path: str = LIB_PATH):
 def _fl(host=False, mapped=False, cached=False, one_pass=False):
     return ((QFEC_PTR_HOST if host else 0) | (QFEC_PTR_MAPPED if mapped else 0)
             | (QFEC_CACHED if cached else 0) | (QFEC_ONE_PASS if one_pass else 0))
+
+
+def pack_received(data_received, fec_received):
+    """The receive maps of qfec_revive_batch: data_received [n, k] bool (data
+    packet i of group g arrived), fec_received [n] bool (its FEC packet
+    arrived) -> uint8 [n, ceil((k + 1) / 8)], bit i of a map being
+    (map[i // 8] >> (i % 8)) & 1, the FEC packet's bit k."""
+    import numpy as np
+    d = np.asarray(data_received, dtype=bool)
+    f = np.asarray(fec_received, dtype=bool)
+    if d.ndim != 2 or f.shape != (d.shape[0],):
+        raise ValueError("data_received is [n, k], fec_received [n]")
+    bits = np.concatenate([d, f[:, None]], axis=1)
+    return np.packbits(bits, axis=1, bitorder="little")
 
 
 class HostBuffer:
@@ -328,6 +351,36 @@ class Context:
             rc = self.lib.qfec_recover_inslot_batch_strided(self.ctx, _ptr(rows), _ptr(missing),
                                                             k, L, rs, gs, n_groups, _ptr(out),
                                                             os_, fl)
+        return self._check(rc)
+
+    def revive(self, rows, parity, received, k, L, n_groups, out=None, *, status,
+               revived_idx=None, revived_list=None, counts=None, row_stride=None,
+               group_stride=None, parity_stride=None, map_stride=None, out_stride=None,
+               cached=False):
+        """qfec_revive_batch: classify every group from its receive map
+        (pack_received) and rebuild the lost packet of the revivable ones, into
+        out or (out=None) in place in rows.  status uint8[n]; revived_idx
+        uint8[n], revived_list uint64[n] and counts uint64[3] are optional.
+        Device pointers only; queued on the context's stream (sync() before
+        reading the results)."""
+        fl = _fl(cached=cached)
+        if row_stride is None and group_stride is None and parity_stride is None \
+                and map_stride is None and out_stride is None:
+            rc = self.lib.qfec_revive_batch(self.ctx, _ptr(rows), _ptr(parity), _ptr(received),
+                                            k, L, n_groups, _ptr(out), _ptr(status),
+                                            _ptr(revived_idx), _ptr(revived_list), _ptr(counts),
+                                            fl)
+        else:
+            rs = L if row_stride is None else row_stride
+            gs = k * rs if group_stride is None else group_stride
+            ps = L if parity_stride is None else parity_stride
+            ms = k // 8 + 1 if map_stride is None else map_stride
+            os_ = L if out_stride is None else out_stride
+            rc = self.lib.qfec_revive_batch_strided(self.ctx, _ptr(rows), _ptr(parity),
+                                                    _ptr(received), k, L, rs, gs, ps, ms,
+                                                    n_groups, _ptr(out), os_, _ptr(status),
+                                                    _ptr(revived_idx), _ptr(revived_list),
+                                                    _ptr(counts), fl)
         return self._check(rc)
 
     # -- ragged ------------------------------------------------------------
