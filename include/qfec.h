@@ -325,6 +325,53 @@ int qfec_recover_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt
                         const uint8_t* parity, const uint64_t* parity_off,
                         const uint16_t* parity_len, const uint8_t* missing_idx, uint8_t* out,
                         const uint64_t* out_off, uint32_t flags);
+/* qfec_revive_batch for a ragged batch: the receiver's decision and the revive
+ * in one call, with k per group from grp_ptr.  bytes .. parity_len, out and
+ * out_off are exactly as for qfec_recover_ragged; group g has
+ * k_g = grp_ptr[g+1] - grp_ptr[g] packets, its slot i is packet grp_ptr[g] + i.
+ * received: the map of group g is map_stride bytes at received + g*map_stride,
+ *   bits as for qfec_revive_batch: bits 0 .. k_g-1 the data packets, bit k_g
+ *   the FEC packet, higher bits ignored.  map_stride is one value for the
+ *   batch (32 holds any legal group, 2 every group of k <= 15).
+ * The rule, the three QFEC_GROUP_* codes and status (required), revived_idx,
+ * revived_list and counts (each may be NULL) are those of qfec_revive_batch:
+ * revived_idx is 0xFF for groups not revived, revived_list is ascending and
+ * not written from the count on, counts[1] is its length.
+ * A revived group receives parity_len[g] bytes at out + out_off[g]: the parity
+ * XOR every received packet, zero padded -- byte for byte what
+ * qfec_recover_ragged writes for it with missing_idx[g] = m.  There is no
+ * in-place form (a lost ragged packet has no slot of its own): out and out_off
+ * are required.
+ * Never read: the pkt_off / pkt_len entries of a revived group's lost packet;
+ * every pkt_off, pkt_len, parity_off, parity_len and out_off entry and every
+ * payload and parity byte of a complete or unrevivable group; the map of an
+ * invalid group (below).  Never written: out bytes of groups not revived, and
+ * out bytes outside [out_off[g], out_off[g] + parity_len[g]) of revived ones.
+ * Latched on the device and returned by the next qfec_sync as
+ * -QUIC_INVALID_FEC_DATA: a group with k_g = 0, k_g > 255 (a grp_ptr that is
+ * not monotone shows up as that) or k_g / 8 + 1 > map_stride -- it gets status
+ * QFEC_GROUP_UNREVIVABLE and revived_idx 0xFF and is counted as unrevivable;
+ * and, for a revived group, a bad parity_len or a received pkt_len of 0 or
+ * above parity_len[g], exactly as qfec_recover_ragged latches them -- its
+ * status stays QFEC_GROUP_REVIVED (the status states the map), its out bytes
+ * are unspecified, and every other group's outputs are right.
+ * Refused on the host (nothing launched, nothing written): map_stride == 0
+ * (-QUIC_INVALID_FEC_DATA); QFEC_PTR_HOST, QFEC_PTR_MAPPED or QFEC_ASYNC; a
+ * NULL required buffer; n_groups >= 2^32, packet indices being 32 bits
+ * (QFEC_ERR_INTERNAL).  n_groups == 0 succeeds before the buffers are looked
+ * at (counts, if given, receives three zeroes).  QFEC_CACHED and
+ * QFEC_SMALL_GROUPS are accepted and change nothing: the ragged device kernels
+ * are nontemporal only, and one body (eight list entries per 4-wave block) is
+ * built.  Like qfec_revive_batch the call only queues kernels on the
+ * context's stream, never waits, never reads the revived count back, and uses
+ * the same context-owned scratch. */
+int qfec_revive_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt_off,
+                       const uint16_t* pkt_len, const uint32_t* grp_ptr, uint64_t n_groups,
+                       const uint8_t* parity, const uint64_t* parity_off,
+                       const uint16_t* parity_len, const uint8_t* received, uint64_t map_stride,
+                       uint8_t* out, const uint64_t* out_off, uint8_t* status,
+                       uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
+                       uint32_t flags);
 
 /* ---- single buffer ------------------------------------------------------ */
 /* out[j] ^= in[j] for j < n (QuicFecGroupInterface::XorBuffers). */

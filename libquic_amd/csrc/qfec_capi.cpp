@@ -1425,6 +1425,39 @@ int qfec_recover_inslot_batch(qfec_ctx* ctx, uint8_t* rows, const uint8_t* missi
                                            n_groups, out, L, flags);
 }
 
+namespace {
+
+// The revive scratch of both revive calls (fixed-shape and ragged), before
+// their launches: grown to revive_scratch_bytes(n_groups) -- the outgrown block
+// is retired, not freed: hipFree would wait for the device -- and ordered after
+// the last revive call's kernels if that call ran on another stream.
+int revive_scratch_acquire(qfec_ctx* ctx, uint64_t n_groups) {
+  const uint64_t need = qfec::revive_scratch_bytes(n_groups);
+  if (ctx->revive_bytes < need) {
+    const size_t want = std::max<size_t>({(size_t)need, 2 * ctx->revive_bytes, 4096});
+    void* grown = nullptr;
+    QFEC_HIP(ctx, hipMalloc(&grown, want));
+    if (ctx->d_revive) ctx->revive_retired.push_back(ctx->d_revive);
+    ctx->d_revive = grown;
+    ctx->revive_bytes = want;
+  }
+  if (!ctx->revive_done)
+    QFEC_HIP(ctx, hipEventCreateWithFlags(&ctx->revive_done, hipEventDisableTiming));
+  if (ctx->revive_recorded && ctx->revive_stream != ctx->stream)
+    QFEC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->revive_done, 0));
+  return QFEC_OK;
+}
+
+// After a revive call's launches: the event a call on another stream waits for.
+int revive_scratch_release(qfec_ctx* ctx) {
+  QFEC_HIP(ctx, hipEventRecord(ctx->revive_done, ctx->stream));
+  ctx->revive_stream = ctx->stream;
+  ctx->revive_recorded = true;
+  return QFEC_OK;
+}
+
+}  // namespace
+
 // Revive from per-group receive maps: the receiver half of QuicFecGroup
 // (NumMissingPackets / CanRevive / IsFinished + Revive) for a device-resident
 // batch.  The call only queues kernels on the context's stream: the revived
@@ -1457,20 +1490,7 @@ int qfec_revive_batch_strided(qfec_ctx* ctx, uint8_t* rows, const uint8_t* parit
   if (!rows || !parity || !received || !status) return fail(ctx, QFEC_ERR_INTERNAL, "null buffer");
   if (n_groups >= (1ull << 56))
     return fail(ctx, QFEC_ERR_INTERNAL, "more than 2^56 groups");
-  const uint64_t need = qfec::revive_scratch_bytes(n_groups);
-  if (ctx->revive_bytes < need) {
-    // the outgrown block is retired, not freed: hipFree would wait for the device
-    const size_t want = std::max<size_t>({(size_t)need, 2 * ctx->revive_bytes, 4096});
-    void* grown = nullptr;
-    QFEC_HIP(ctx, hipMalloc(&grown, want));
-    if (ctx->d_revive) ctx->revive_retired.push_back(ctx->d_revive);
-    ctx->d_revive = grown;
-    ctx->revive_bytes = want;
-  }
-  if (!ctx->revive_done)
-    QFEC_HIP(ctx, hipEventCreateWithFlags(&ctx->revive_done, hipEventDisableTiming));
-  if (ctx->revive_recorded && ctx->revive_stream != ctx->stream)
-    QFEC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->revive_done, 0));
+  if ((rc = revive_scratch_acquire(ctx, n_groups))) return rc;
   qfec::ReviveArgs a{};
   a.rows = rows;
   a.parity = parity;
@@ -1491,10 +1511,7 @@ int qfec_revive_batch_strided(qfec_ctx* ctx, uint8_t* rows, const uint8_t* parit
   a.ncu = ctx->ncu;
   qfec::revive_scratch_layout(a, ctx->d_revive);
   QFEC_HIP(ctx, qfec::launch_revive(a, (flags & QFEC_CACHED) == 0, ctx->stream));
-  QFEC_HIP(ctx, hipEventRecord(ctx->revive_done, ctx->stream));
-  ctx->revive_stream = ctx->stream;
-  ctx->revive_recorded = true;
-  return QFEC_OK;
+  return revive_scratch_release(ctx);
 }
 
 int qfec_revive_batch(qfec_ctx* ctx, uint8_t* rows, const uint8_t* parity, const uint8_t* received,
@@ -2034,6 +2051,62 @@ int qfec_recover_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt
   a.err = ctx->d_err;
   QFEC_HIP(ctx, qfec::launch_ragged(a, true, ctx->stream, (flags & QFEC_SMALL_GROUPS) != 0));
   return QFEC_OK;
+}
+
+// qfec_revive_batch for a ragged CSR batch: classify / scan / emit with k per
+// group from grp_ptr, then the ragged recover block body over the work list.
+// Queues only, like the fixed-shape call, and shares its scratch.
+int qfec_revive_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt_off,
+                       const uint16_t* pkt_len, const uint32_t* grp_ptr, uint64_t n_groups,
+                       const uint8_t* parity, const uint64_t* parity_off,
+                       const uint16_t* parity_len, const uint8_t* received, uint64_t map_stride,
+                       uint8_t* out, const uint64_t* out_off, uint8_t* status,
+                       uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
+                       uint32_t flags) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (map_stride == 0)
+    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+                "receive map stride 0: a group of k packets needs k / 8 + 1 bytes");
+  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "ragged revive from receive maps: device pointers only, queued on the context's "
+                "stream (QFEC_PTR_HOST, QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)");
+  if (n_groups == 0) {
+    if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(uint64_t), ctx->stream));
+    return QFEC_OK;
+  }
+  if (!bytes || !pkt_off || !pkt_len || !grp_ptr || !parity || !parity_off || !parity_len ||
+      !received || !out || !out_off || !status)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "ragged revive: null buffer (only revived_idx, revived_list and counts may be "
+                "NULL)");
+  if (n_groups >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "ragged revive: 2^32 or more groups (packet indices are 32 bits)");
+  if ((rc = revive_scratch_acquire(ctx, n_groups))) return rc;
+  qfec::ReviveRaggedArgs a{};
+  a.bytes = bytes;
+  a.pkt_off = pkt_off;
+  a.pkt_len = pkt_len;
+  a.grp_ptr = grp_ptr;
+  a.parity = parity;
+  a.parity_off = parity_off;
+  a.parity_len = parity_len;
+  a.out = out;
+  a.out_off = out_off;
+  a.received = received;
+  a.map_stride = map_stride;
+  a.n_groups = n_groups;
+  a.status = status;
+  a.revived_idx = revived_idx;
+  a.revived_list = revived_list;
+  a.counts = counts;
+  a.err = ctx->d_err;
+  a.ncu = ctx->ncu;
+  qfec::revive_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_revive_ragged(a, ctx->stream));
+  return revive_scratch_release(ctx);
 }
 
 int qfec_xor_into(qfec_ctx* ctx, const uint8_t* in, uint64_t n, uint8_t* out, uint32_t flags) {

@@ -142,6 +142,46 @@ struct RaggedArgs {
   uint32_t done_token;
 };
 
+// Revive from per-group receive maps over a ragged CSR batch
+// (qfec_revive_ragged): the RaggedArgs tables of a recover, the maps and the
+// outputs / scratch of ReviveArgs.  A struct of its own: a field added to
+// ReviveArgs would move the kernarg offsets of the fixed-shape revive kernels.
+struct ReviveRaggedArgs {
+  const uint8_t* bytes;
+  const uint64_t* pkt_off;
+  const uint16_t* pkt_len;
+  const uint32_t* grp_ptr;
+  const uint8_t* parity;
+  const uint64_t* parity_off;
+  const uint16_t* parity_len;
+  uint8_t* out;
+  const uint64_t* out_off;
+  const uint8_t* received;
+  uint64_t map_stride;
+  uint64_t n_groups;  // < 2^32 (packet indices are 32 bits)
+  uint8_t* status;
+  uint8_t* revived_idx;    // nullable
+  uint64_t* revived_list;  // nullable
+  uint64_t* counts;        // nullable: [complete, revived, unrevivable]
+  // scratch, as ReviveArgs (revive_scratch_bytes(n_groups))
+  uint32_t* tile_cnt;
+  uint64_t* tile_off;
+  uint64_t* totals;
+  uint64_t* work;
+  uint32_t* err;
+  uint32_t ncu;
+};
+inline void revive_scratch_layout(ReviveRaggedArgs& a, void* block) {
+  uint8_t* p = static_cast<uint8_t*>(block);
+  a.totals = reinterpret_cast<uint64_t*>(p);
+  a.work = reinterpret_cast<uint64_t*>(p + 32);
+  a.tile_off = a.work + a.n_groups + kReviveListPad;
+  a.tile_cnt = reinterpret_cast<uint32_t*>(a.tile_off + revive_tiles(a.n_groups));
+}
+// Four launches on s (classify, scan, emit, the ragged block body over the
+// work list), ordered by the stream alone.  n_groups > 0.
+hipError_t launch_revive_ragged(const ReviveRaggedArgs& a, hipStream_t s);
+
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch
 // per batch (the launch is most of a small flush's connection-thread cost).

@@ -28,7 +28,9 @@
 //    writes into grid-wide phases (0.80 of 8 TB/s on any buffer placement).
 //  * Revive from receive maps (qfec_revive_batch): classify / scan / emit build
 //    a packed list of the revivable groups on the device, and the recover
-//    body above runs over that list only (revive_xor_kernel).
+//    body above runs over that list only (revive_xor_kernel); for ragged
+//    batches (qfec_revive_ragged) the same three kernels with k per group and
+//    the ragged block body over the list (revive_ragged_kernel).
 //  * Ragged CSR batches: eight groups per 4-wave block in one flat window
 //    space (ragged_block_kernel; the one-group body below is its exact
 //    fallback; the round-1/2 forms, one and two groups per wave, live in
@@ -737,15 +739,41 @@ __device__ __forceinline__ uint32_t revive_classify(const uint8_t* mp, uint32_t 
 // EMIT = false: status, revived_idx and the tile's counts.  EMIT = true: the
 // work list and revived_list, at tile_off[tile] + the group's rank among the
 // tile's revived groups (wave ballots, the waves' counts through LDS).
-template <bool EMIT>
-__global__ __launch_bounds__(kReviveTile) void revive_classify_kernel(ReviveArgs a) {
+// Args: ReviveArgs (one k for the batch, every group legal) or
+// ReviveRaggedArgs (k per group from grp_ptr; a group of 0 or more than 255
+// packets, or whose k + 1 bits do not fit map_stride, is unrevivable and
+// latches kErrGroupSize -- its map is not read).
+__device__ __forceinline__ bool revive_group_k(const ReviveArgs& a, uint64_t, uint32_t& k) {
+  k = a.k;
+  return true;
+}
+__device__ __forceinline__ bool revive_group_k(const ReviveRaggedArgs& a, uint64_t g,
+                                               uint32_t& k) {
+  k = a.grp_ptr[g + 1] - a.grp_ptr[g];  // a non-monotone grp_ptr shows up as k > 255
+  return k >= 1u && k <= 255u && (uint64_t)(k / 8u + 1u) <= a.map_stride;
+}
+__device__ __forceinline__ void revive_bad_group(const ReviveArgs&) {}
+__device__ __forceinline__ void revive_bad_group(const ReviveRaggedArgs& a) {
+  atomicOr(a.err, kErrGroupSize);
+}
+
+template <bool EMIT, typename Args>
+__global__ __launch_bounds__(kReviveTile) void revive_classify_kernel(Args a) {
   __shared__ uint32_t s_w[kReviveTile / 64];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
   for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     const uint64_t g = tile * kReviveTile + tid;
     uint32_t st = 3u, m = 0xFFu;  // 3: past the batch
-    if (g < a.n_groups) st = revive_classify(a.received + g * a.map_stride, a.k, m);
+    if (g < a.n_groups) {
+      uint32_t k;
+      if (revive_group_k(a, g, k)) {
+        st = revive_classify(a.received + g * a.map_stride, k, m);
+      } else {
+        st = kGroupUnrevivable;
+        if constexpr (!EMIT) revive_bad_group(a);
+      }
+    }
     const uint64_t brev = __ballot(st == kGroupRevived);
     if constexpr (!EMIT) {
       const uint64_t bcomp = __ballot(st == kGroupComplete);
@@ -776,7 +804,8 @@ static_assert(kReviveTile == 256, "four waves' counts are summed by hand above")
 // One workgroup: tile_off[i] = revived groups in tiles before i, then the
 // totals.  A tile of the scan is kRvScanBlock counts; the running bases are
 // uniform registers.
-__global__ __launch_bounds__(kRvScanBlock) void revive_scan_kernel(ReviveArgs a) {
+template <typename Args>
+__global__ __launch_bounds__(kRvScanBlock) void revive_scan_kernel(Args a) {
   __shared__ uint32_t s_rev[kRvScanBlock / 64], s_comp[kRvScanBlock / 64];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
@@ -1103,14 +1132,26 @@ struct GroupPrefetch {
   u32x4 pw0, pw1;                // recover: parity windows lane, lane + 64
 };
 
-template <bool RECOVER>
-__device__ __forceinline__ void group_scalars(const RaggedArgs& a, uint64_t g, GroupPrefetch& f) {
+// Work-list entry g << 8 | m of a ragged revive (g < 2^32), taken apart with
+// 32-bit shifts.
+__device__ __forceinline__ void list_entry(uint64_t e, uint64_t& g, uint32_t& m) {
+  const uint32_t lo = (uint32_t)e, hi = (uint32_t)(e >> 32);
+  g = (uint64_t)((lo >> 8) | (hi << 24));
+  m = lo & 0xFFu;
+}
+
+// LIST (recover): m is the work-list entry's (qfec_revive_ragged), a.missing is
+// not read.
+template <bool RECOVER, bool LIST = false>
+__device__ __forceinline__ void group_scalars(const RaggedArgs& a, uint64_t g, GroupPrefetch& f,
+                                              uint32_t list_m = 0) {
   f.p0 = a.grp_ptr[g];
   f.k = a.grp_ptr[g + 1] - f.p0;
   f.m = 0xFFFFFFFFu;
   f.plen = 0;
   if constexpr (RECOVER) {
-    f.m = a.missing[g];
+    if constexpr (LIST) f.m = list_m;
+    else f.m = a.missing[g];
     f.plen = a.parity_len[g];
     f.dst_off = a.out_off[g];
   } else {
@@ -1376,9 +1417,20 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t lane, u
 // exact); 8 = parity stores through the caches (not nontemporal); 16 = payload
 // loads through the caches (both exact: the cache-policy probe of round 6);
 // bits 5-7 = P != 0: parity stores with explicit policy st16pol<P> (exact).
-template <bool RECOVER, int WAVES, int GPB, int U = 2, bool PF = true, bool AL = true, int DIAG = 0>
-__device__ __forceinline__ void ragged_block_body(const RaggedArgs& a) {
+// LIST (recover, qfec_revive_ragged): group slot j of the block is not group
+// g0 + j with m = a.missing[g0 + j] but work-list entry step * GPB + j
+// (g << 8 | m) of a list of `count` entries; a.missing and a.n_groups are not
+// used.  The list is readable past the count but holds nothing there: only
+// slots below the count are ever turned into a group.  Every return of the
+// body is block-uniform, so a kernel may call it once per list step with a
+// barrier between the steps (revive_ragged_kernel).
+template <bool RECOVER, int WAVES, int GPB, int U = 2, bool PF = true, bool AL = true, int DIAG = 0,
+          bool LIST = false>
+__device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
+                                                  const uint64_t* __restrict__ work = nullptr,
+                                                  uint64_t count = 0, uint64_t step = 0) {
   static_assert(GPB >= 2 && GPB <= 64, "group slots are lanes of wave 0");
+  static_assert(!LIST || RECOVER, "the work list is a receiver's");
   constexpr uint32_t NT = 64u * WAVES;
   constexpr uint32_t NBLK = NT;        // 64-window blocks: CAPW = 64 NT windows
   constexpr uint32_t CAPW = 64u * NBLK;
@@ -1397,9 +1449,11 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a) {
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = lane_id();
   const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint64_t g0 = (uint64_t)blockIdx.x * GPB;
-  if (g0 >= a.n_groups) return;  // block-uniform
-  const uint32_t ng = (uint32_t)min<uint64_t>((uint64_t)GPB, a.n_groups - g0);
+  // LIST: g0 is the step's first list entry and the entries number `count`
+  const uint64_t g0 = LIST ? step * GPB : (uint64_t)blockIdx.x * GPB;
+  const uint64_t gn = LIST ? count : a.n_groups;
+  if (g0 >= gn) return;  // block-uniform
+  const uint32_t ng = (uint32_t)min<uint64_t>((uint64_t)GPB, gn - g0);
   s_head[tid] = 0ull;  // NBLK == NT
   // ---- 1. group scalars (wave 0, lane j = group slot j)
   if (wv == 0u) {
@@ -1407,16 +1461,18 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a) {
     uint64_t d = 0, po = 0;
     bool ok = true;
     if (lane < ng) {
-      p0 = a.grp_ptr[g0 + lane];
-      k = a.grp_ptr[g0 + lane + 1] - p0;
+      uint64_t g = g0 + lane;
+      if constexpr (LIST) list_entry(work[g0 + lane], g, m);
+      p0 = a.grp_ptr[g];
+      k = a.grp_ptr[g + 1] - p0;
       if constexpr (RECOVER) {
-        m = a.missing[g0 + lane];
-        pl = a.parity_len[g0 + lane];
-        d = a.out_off[g0 + lane];
-        po = a.parity_off[g0 + lane];
+        if constexpr (!LIST) m = a.missing[g0 + lane];
+        pl = a.parity_len[g];
+        d = a.out_off[g];
+        po = a.parity_off[g];
         ok = m < k && pl >= 16u && pl <= kMaxPacket;
       } else {
-        d = a.parity_off[g0 + lane];
+        d = a.parity_off[g];
       }
       ok = ok && k >= 1u && k <= 255u;
       r = ok ? (RECOVER ? k - 1u : k) : 0u;
@@ -1472,10 +1528,13 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a) {
     uint32_t* fb = s_raw + wv * kFbWords;
     for (uint32_t jj = wv; jj < ng; jj += WAVES) {
       GroupPrefetch f;
-      group_scalars<RECOVER>(a, g0 + jj, f);
-      group_vectors<RECOVER, true>(a, g0 + jj, lane, f);
+      uint64_t g = g0 + jj;
+      uint32_t lm = 0;
+      if constexpr (LIST) list_entry(work[g0 + jj], g, lm);  // jj < ng: below the count
+      group_scalars<RECOVER, LIST>(a, g, f, lm);
+      group_vectors<RECOVER, true>(a, g, lane, f);
       wave_lds_order();
-      ragged_group<RECOVER, true, 2, 1>(a, g0 + jj, lane, f, fb,
+      ragged_group<RECOVER, true, 2, 1>(a, g, lane, f, fb,
                                         reinterpret_cast<uint64_t*>(fb + 4u * kParWin),
                                         reinterpret_cast<u32x4*>(fb + 6u * kParWin));
       wave_lds_order();
@@ -1625,6 +1684,36 @@ template <bool RECOVER, int WAVES, int GPB, int U = 2, bool PF = true, bool AL =
 __global__ __launch_bounds__(64 * WAVES) void ragged_block_kernel(RaggedArgs a) {
   ragged_block_body<RECOVER, WAVES, GPB, U, PF, AL, DIAG>(a);
   ragged_signal_done(a);
+}
+
+// qfec_revive_ragged's fourth kernel: the recover block body over the packed
+// work list of the revivable groups (classify / scan / emit above), GPB list
+// entries per step.  The count stays on the device: the grid is sized by the
+// device and its blocks loop over the list steps; the body's early returns end
+// a step (all block-uniform), and the barrier keeps a step's LDS from the next
+// one's writes.  `work` and `totals` are restrict parameters of their own, as
+// for revive_xor_kernel.
+template <int WAVES, int GPB>
+__global__ __launch_bounds__(64 * WAVES) void revive_ragged_kernel(
+    ReviveRaggedArgs v, const uint64_t* __restrict__ work, const uint64_t* __restrict__ totals) {
+  RaggedArgs a{};
+  a.bytes = v.bytes;
+  a.pkt_off = v.pkt_off;
+  a.pkt_len = v.pkt_len;
+  a.grp_ptr = v.grp_ptr;
+  a.parity = v.parity;
+  a.parity_off = v.parity_off;
+  a.parity_len = v.parity_len;
+  a.out = v.out;
+  a.out_off = v.out_off;
+  a.n_groups = v.n_groups;
+  a.err = v.err;
+  const uint64_t count = totals[kGroupRevived];
+  const uint64_t nstep = (count + GPB - 1) / GPB;
+  for (uint64_t step = blockIdx.x; step < nstep; step += gridDim.x) {
+    ragged_block_body<true, WAVES, GPB, 2, true, true, 0, true>(a, work, count, step);
+    __syncthreads();  // the step's LDS reads are done before the next step's writes
+  }
 }
 
 
@@ -2893,12 +2982,14 @@ hipError_t launch_revive(const ReviveArgs& a, bool nontemporal, hipStream_t s) {
   if (a.n_groups == 0) return hipSuccess;
   // classify and emit: grid-stride over the tiles of kReviveTile groups
   const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
-  hipLaunchKernelGGL(revive_classify_kernel<false>, dim3(cgrid), dim3(kReviveTile), 0, s, a);
+  hipLaunchKernelGGL((revive_classify_kernel<false, ReviveArgs>), dim3(cgrid), dim3(kReviveTile), 0,
+                     s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(revive_scan_kernel, dim3(1), dim3(kRvScanBlock), 0, s, a);
+  hipLaunchKernelGGL(revive_scan_kernel<ReviveArgs>, dim3(1), dim3(kRvScanBlock), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(revive_classify_kernel<true>, dim3(cgrid), dim3(kReviveTile), 0, s, a);
+  hipLaunchKernelGGL((revive_classify_kernel<true, ReviveArgs>), dim3(cgrid), dim3(kReviveTile), 0,
+                     s, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // revive: the count stays on the device, so the grid is sized by the device
   // (eight workgroups per CU: every wave slot at up to 64 VGPRs) and by the
@@ -2921,6 +3012,38 @@ hipError_t launch_revive(const ReviveArgs& a, bool nontemporal, hipStream_t s) {
 }
 
 constexpr int kRaggedBlockWaves = 4, kRaggedBlockGroups = 8;  // ragged_block_kernel shape
+
+hipError_t launch_revive_ragged(const ReviveRaggedArgs& a, hipStream_t s) {
+  if (a.n_groups == 0) return hipSuccess;
+  const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
+  hipLaunchKernelGGL((revive_classify_kernel<false, ReviveRaggedArgs>), dim3(cgrid),
+                     dim3(kReviveTile), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(revive_scan_kernel<ReviveRaggedArgs>, dim3(1), dim3(kRvScanBlock), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL((revive_classify_kernel<true, ReviveRaggedArgs>), dim3(cgrid),
+                     dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  // the count stays on the device: as many blocks as the device holds at once
+  // (asked of the runtime: with the VGPRs of this build six per CU, and a grid
+  // of eight per CU left a quarter of the blocks to run after the others, at a
+  // third of the device: 1.35x the dense recover with every group revived) or
+  // the worst case, whichever is smaller; the blocks loop over the list steps
+  static const int per_cu = [] {
+    int nb = 0;
+    const hipError_t q = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &nb, revive_ragged_kernel<kRaggedBlockWaves, kRaggedBlockGroups>, 64 * kRaggedBlockWaves,
+        0);
+    return q == hipSuccess && nb > 0 ? nb : 4;
+  }();
+  const uint64_t resident = (uint64_t)(a.ncu ? a.ncu : 256u) * (uint64_t)per_cu;
+  const uint64_t steps = (a.n_groups + kRaggedBlockGroups - 1) / kRaggedBlockGroups;
+  hipLaunchKernelGGL((revive_ragged_kernel<kRaggedBlockWaves, kRaggedBlockGroups>),
+                     dim3((uint32_t)std::min(steps, resident)), dim3(64 * kRaggedBlockWaves), 0, s,
+                     a, a.work, a.totals);
+  return hipGetLastError();
+}
 
 hipError_t launch_ragged(const RaggedArgs& a0, bool recover, hipStream_t s, bool small_groups) {
   if (a0.n_groups == 0) return hipSuccess;

@@ -76,6 +76,9 @@ SIGNATURES = [
       C.c_uint64, C.c_uint64, _u8p, C.c_uint64, _u8p, _u8p, _vp, _vp, C.c_uint32]),
     ("qfec_encode_ragged", C.c_int,
      [_vp, _u8p, _vp, _vp, _vp, C.c_uint64, _u8p, _vp, _vp, C.c_uint32]),
+    ("qfec_revive_ragged", C.c_int,
+     [_vp, _u8p, _vp, _vp, _vp, C.c_uint64, _u8p, _vp, _vp, _u8p, C.c_uint64, _u8p, _vp, _u8p,
+      _u8p, _vp, _vp, C.c_uint32]),
     ("qfec_recover_ragged", C.c_int,
      [_vp, _u8p, _vp, _vp, _vp, C.c_uint64, _u8p, _vp, _vp, _u8p, _u8p, _vp, C.c_uint32]),
     ("qfec_xor_into", C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint32]),
@@ -181,6 +184,39 @@ def pack_received(data_received, fec_received):
     if d.ndim != 2 or f.shape != (d.shape[0],):
         raise ValueError("data_received is [n, k], fec_received [n]")
     bits = np.concatenate([d, f[:, None]], axis=1)
+    return np.packbits(bits, axis=1, bitorder="little")
+
+
+def pack_received_ragged(received, fec_received, grp_ptr, map_stride=None):
+    """The receive maps of qfec_revive_ragged: received bool per packet in CSR
+    order, fec_received bool per group, grp_ptr [n + 1] -> uint8 [n,
+    map_stride]; bit i of group g's map is data packet grp_ptr[g] + i, bit k_g
+    its FEC packet.  map_stride=None: max_g(k_g // 8 + 1).  ValueError for a
+    group outside 1..255 packets or a map_stride too small for some group."""
+    import numpy as np
+    ptr = np.asarray(grp_ptr).astype(np.int64).ravel()
+    f = np.asarray(fec_received, dtype=bool).ravel()
+    r = np.asarray(received, dtype=bool).ravel()
+    n = ptr.size - 1
+    if n < 0 or f.size != n:
+        raise ValueError("grp_ptr is [n + 1], fec_received [n]")
+    ks = np.diff(ptr)
+    if n and (ks.min() < 1 or ks.max() > MAX_GROUP_PACKETS):
+        raise ValueError("a FEC group has 1..%d packets" % MAX_GROUP_PACKETS)
+    if n and (ptr[0] < 0 or r.size < ptr[-1]):
+        raise ValueError("received is shorter than grp_ptr[n]")
+    need = int(ks.max()) // 8 + 1 if n else 1
+    if map_stride is None:
+        map_stride = need
+    if map_stride < need:
+        raise ValueError("map_stride %d below the %d bytes of the largest group's map"
+                         % (map_stride, need))
+    bits = np.zeros((n, 8 * map_stride), dtype=bool)
+    if n:
+        g = np.repeat(np.arange(n), ks)
+        i = np.arange(ptr[0], ptr[-1]) - np.repeat(ptr[:-1], ks)
+        bits[g, i] = r[ptr[0]:ptr[-1]]
+        bits[np.arange(n), ks] = f
     return np.packbits(bits, axis=1, bitorder="little")
 
 
@@ -403,6 +439,22 @@ class Context:
                                           _ptr(out), _ptr(out_off),
                                           _fl(host, mapped) | (QFEC_ASYNC if async_ else 0)
                                           | (QFEC_SMALL_GROUPS if small_groups else 0))
+        return self._check(rc)
+
+    def revive_ragged(self, data, pkt_off, pkt_len, grp_ptr, n_groups, parity, parity_off,
+                      parity_len, received, map_stride, out, out_off, *, status,
+                      revived_idx=None, revived_list=None, counts=None):
+        """qfec_revive_ragged: classify every group of a CSR batch from its
+        receive map (pack_received_ragged) and write the lost packet of the
+        revivable ones to out + out_off[g].  status uint8[n]; revived_idx
+        uint8[n], revived_list uint64[n] and counts uint64[3] are optional.
+        Device pointers only; queued on the context's stream (sync() before
+        reading the results)."""
+        rc = self.lib.qfec_revive_ragged(self.ctx, _ptr(data), _ptr(pkt_off), _ptr(pkt_len),
+                                         _ptr(grp_ptr), n_groups, _ptr(parity),
+                                         _ptr(parity_off), _ptr(parity_len), _ptr(received),
+                                         map_stride, _ptr(out), _ptr(out_off), _ptr(status),
+                                         _ptr(revived_idx), _ptr(revived_list), _ptr(counts), 0)
         return self._check(rc)
 
     def xor_into(self, src, n, dst, *, host=False, mapped=False):
