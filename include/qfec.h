@@ -15,6 +15,10 @@
  *       Send-side hook: QuicPacketCreator::SerializePacket between
  *       QuicFramer::BuildDataPacket and EncryptInPlace
  *       (src/net/quic/core/quic_packet_creator.cc:517-563, :530, :549).
+ *   qfec_accumulate_ragged
+ *       is UpdateParity's per-turn form: the packets at hand folded into one
+ *       running row per open group (on a receiver Update / UpdateFec as well:
+ *       the row is then what Revive() copies out).
  *   qfec_recover_batch / _strided / qfec_recover_ragged
  *       replaces QuicFecGroup::UpdateFec + Update(received) + CanRevive() +
  *       Revive().  Receive-side hook: QuicConnection::ProcessValidatedPacket
@@ -372,6 +376,56 @@ int qfec_revive_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt_
                        uint8_t* out, const uint64_t* out_off, uint8_t* status,
                        uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
                        uint32_t flags);
+
+/* The running accumulator of QuicFecGroup::UpdateParity (and, on a receiver,
+ * Update / UpdateFec), batched: fold this turn's packets of every open group
+ * into one row per group, so the packets' buffers can be recycled before the
+ * group closes.  bytes, pkt_off, pkt_len and grp_ptr are the CSR tables of
+ * qfec_encode_ragged and list, per group, the packets to fold NOW: data
+ * packets and, on a receiver, the FEC packet's redundancy (just another
+ * packet).  Group g folds into accumulator s = slot[g] (slot == NULL: s = g,
+ * lockstep batches): the row acc + s * acc_stride, its length acc_len[s] read
+ * on entry and written on exit.
+ * The rule, per group, with old = acc_len[s] and
+ * new = max(old, max pkt_len of the group's packets):
+ *   for j < new: acc[s][j] = (j < old ? acc[s][j] : 0)
+ *                            XOR (XOR over this turn's packets with j < len_i of p_i[j]);
+ *   acc_len[s] = new.
+ * Row bytes at or beyond old count as zero whatever they hold: acc_len[s] == 0
+ * is a fresh slot and needs no clearing.  A sender's row is the FEC packet's
+ * redundancy (qfec_encode_ragged's parity and length) once the group's packets
+ * have been folded; a receiver's row is the revived packet
+ * (qfec_recover_ragged's output, length parity_len) once the k-1 received data
+ * packets and the redundancy have been folded -- in any order, over any number
+ * of calls.
+ * A group with no packets this turn (k_g = 0) is valid and a no-op: its row
+ * and length keep their values.
+ * Never read: a row whose old length is 0; row bytes at or beyond old; rows and
+ * lengths of slots that no group names.  Never written: row bytes at or beyond
+ * new; rows and lengths of slots that no group names.
+ * The caller guarantees, unchecked: the slots named in one call are distinct
+ * (results for a slot named twice are unspecified), and no acc row overlaps
+ * bytes.
+ * Latched on the device and returned by the next qfec_sync as
+ * -QUIC_INVALID_FEC_DATA: k_g > 255 (a grp_ptr that is not monotone shows up
+ * as that); slot[g] >= n_slots (its acc_len is then not read);
+ * acc_len[s] > min(1452, acc_stride); a pkt_len of 0 or above
+ * min(1452, acc_stride).  The offending group's row and length are left
+ * untouched and every other group's outputs are right.
+ * Refused on the host (nothing launched, nothing written): acc_stride == 0
+ * (-QUIC_INVALID_FEC_DATA); QFEC_PTR_HOST, QFEC_PTR_MAPPED or QFEC_ASYNC; a
+ * NULL bytes, pkt_off, pkt_len, grp_ptr, acc or acc_len; n_groups >= 2^32 or
+ * n_slots >= 2^32; slot == NULL with n_slots < n_groups (QFEC_ERR_INTERNAL).
+ * n_groups == 0 succeeds before the buffers are looked at.  QFEC_CACHED and
+ * QFEC_SMALL_GROUPS are accepted and change nothing.  Device pointers only; the
+ * call only queues kernels on the context's stream, never waits and never
+ * reads anything back; results are valid after qfec_sync, and two calls queued
+ * back to back on one stream see each other's rows (turn t+1 reads what turn
+ * t wrote). */
+int qfec_accumulate_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt_off,
+                           const uint16_t* pkt_len, const uint32_t* grp_ptr, uint64_t n_groups,
+                           uint8_t* acc, uint64_t acc_stride, uint16_t* acc_len,
+                           const uint32_t* slot, uint64_t n_slots, uint32_t flags);
 
 /* ---- single buffer ------------------------------------------------------ */
 /* out[j] ^= in[j] for j < n (QuicFecGroupInterface::XorBuffers). */

@@ -2109,6 +2109,54 @@ int qfec_revive_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt_
   return revive_scratch_release(ctx);
 }
 
+// The running accumulator of QuicFecGroup::UpdateParity / Update / UpdateFec,
+// batched: this turn's packets of each group folded into the group's row.
+// Queues one kernel (per grid of groups); every check that needs the tables
+// is the kernel's.
+int qfec_accumulate_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt_off,
+                           const uint16_t* pkt_len, const uint32_t* grp_ptr, uint64_t n_groups,
+                           uint8_t* acc, uint64_t acc_stride, uint16_t* acc_len,
+                           const uint32_t* slot, uint64_t n_slots, uint32_t flags) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  ctx->last_ticket = 0;
+  if (ctx->debug_fail)
+    return fail(ctx, QFEC_ERR_INTERNAL, "launch failure injected (qfec_debug_fail_launches)");
+  if (acc_stride == 0)
+    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+                "accumulator stride 0: a row holds the longest packet folded into it");
+  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "ragged accumulate: device pointers only, queued on the context's stream "
+                "(QFEC_PTR_HOST, QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)");
+  if (n_groups == 0) return QFEC_OK;
+  if (!bytes || !pkt_off || !pkt_len || !grp_ptr || !acc || !acc_len)
+    return fail(ctx, QFEC_ERR_INTERNAL, "ragged accumulate: null buffer (only slot may be NULL)");
+  if (n_groups >= (1ull << 32) || n_slots >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "ragged accumulate: 2^32 or more groups or slots (packet and slot indices are "
+                "32 bits)");
+  if (!slot && n_slots < n_groups)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "ragged accumulate: slot == NULL folds group g into slot g, and there are fewer "
+                "slots than groups");
+  qfec::AccumulateRaggedArgs a{};
+  a.bytes = bytes;
+  a.pkt_off = pkt_off;
+  a.pkt_len = pkt_len;
+  a.grp_ptr = grp_ptr;
+  a.acc = acc;
+  a.acc_stride = acc_stride;
+  a.acc_len = acc_len;
+  a.slot = slot;
+  a.n_groups = n_groups;
+  a.n_slots = (uint32_t)n_slots;
+  a.lim = (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
+  a.err = ctx->d_err;
+  QFEC_HIP(ctx, qfec::launch_accumulate_ragged(a, ctx->stream));
+  return QFEC_OK;
+}
+
 int qfec_xor_into(qfec_ctx* ctx, const uint8_t* in, uint64_t n, uint8_t* out, uint32_t flags) {
   int rc = bind(ctx);
   if (rc) return rc;

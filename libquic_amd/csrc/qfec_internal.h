@@ -10,10 +10,12 @@ namespace qfec {
 
 // Bits latched into the context's device error word by kernels.
 enum : uint32_t {
-  kErrMissingIndex = 1u,  // missing_idx >= k
+  kErrMissingIndex = 1u,  // missing_idx >= k; accumulate: slot >= n_slots
   kErrPacketLength = 2u,  // ragged packet length 0 or > kMaxPacketSize, or > parity_len
-  kErrGroupSize = 4u,     // ragged group with 0 or > 255 packets
-  kErrParityLength = 8u,  // ragged parity_len 0 or > kMaxPacketSize
+                          // (accumulate: > min(kMaxPacketSize, acc_stride))
+  kErrGroupSize = 4u,     // ragged group with 0 or > 255 packets (accumulate: > 255)
+  kErrParityLength = 8u,  // ragged parity_len 0 or > kMaxPacketSize; accumulate:
+                          // acc_len > min(kMaxPacketSize, acc_stride)
 };
 
 // Fixed-shape encode / recover.  parity == nullptr selects encode.
@@ -181,6 +183,31 @@ inline void revive_scratch_layout(ReviveRaggedArgs& a, void* block) {
 // Four launches on s (classify, scan, emit, the ragged block body over the
 // work list), ordered by the stream alone.  n_groups > 0.
 hipError_t launch_revive_ragged(const ReviveRaggedArgs& a, hipStream_t s);
+
+// Fold a turn's packets into running group parities (qfec_accumulate_ragged):
+// the CSR tables of an encode; group g folds into row acc + s * acc_stride of
+// length acc_len[s], s = slot[g] (slot == nullptr: s = g).  A struct of its
+// own, like ReviveRaggedArgs: RaggedArgs keeps its kernarg layout.
+struct AccumulateRaggedArgs {
+  const uint8_t* bytes;
+  const uint64_t* pkt_off;
+  const uint16_t* pkt_len;
+  const uint32_t* grp_ptr;
+  uint8_t* acc;
+  uint64_t acc_stride;
+  uint16_t* acc_len;     // read on entry, written on exit
+  const uint32_t* slot;  // nullable
+  uint64_t n_groups;     // < 2^32
+  uint32_t n_slots;
+  uint32_t lim;          // min(kMaxPacket, acc_stride): longest packet / row
+  uint32_t* err;
+  // set by launch_accumulate_ragged (a batch beyond one grid is launched in
+  // parts): the identity slot of the part's group 0
+  uint32_t slot_base = 0;
+};
+// The ragged block body, 8 groups per block: one launch on s per
+// 8 * kMaxBlocks256 groups.  n_groups > 0.
+hipError_t launch_accumulate_ragged(const AccumulateRaggedArgs& a, hipStream_t s);
 
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch

@@ -38,6 +38,10 @@
 //    windows of the packets; a window shorter than 16 bytes is loaded as the
 //    16 bytes that end at the packet's last byte and shifted down (zero
 //    fill), so again no load leaves the packet.
+//  * Running group parities (qfec_accumulate_ragged): the same block body in a
+//    third mode beside encode and recover -- the accumulators start from the
+//    caller's rows (zero past their old lengths) and are stored back in place,
+//    the lengths the running maxima (accumulate_ragged_kernel).
 #include "qfec_internal.h"
 
 #include <algorithm>
@@ -1130,7 +1134,13 @@ struct GroupPrefetch {
   uint64_t dst_off;              // parity_off (encode) / out_off (recover)
   uint32_t len, offlo, offhi;    // lane r = received packet r (r < 64)
   u32x4 pw0, pw1;                // recover: parity windows lane, lane + 64
+  // accumulate only: the slot and its length on entry.  The old length stays
+  // a value of its own (plen becomes the new one): the row is zero from `old`
+  // on whatever the new maximum is.  kAccBadSlot: slot >= n_slots, acc_len
+  // not read.
+  uint32_t slot, old;
 };
+constexpr uint32_t kAccBadSlot = 0xFFFFFFFFu;
 
 // Work-list entry g << 8 | m of a ragged revive (g < 2^32), taken apart with
 // 32-bit shifts.
@@ -1142,14 +1152,24 @@ __device__ __forceinline__ void list_entry(uint64_t e, uint64_t& g, uint32_t& m)
 
 // LIST (recover): m is the work-list entry's (qfec_revive_ragged), a.missing is
 // not read.
-template <bool RECOVER, bool LIST = false>
+// ACCUM (encode form, qfec_accumulate_ragged; x its arguments): the slot, its
+// length on entry (not read for a slot out of range) and the row's offset
+// s * acc_stride -- a multiply, no shift.
+template <bool RECOVER, bool LIST = false, bool ACCUM = false>
 __device__ __forceinline__ void group_scalars(const RaggedArgs& a, uint64_t g, GroupPrefetch& f,
-                                              uint32_t list_m = 0) {
+                                              uint32_t list_m = 0,
+                                              const AccumulateRaggedArgs* x = nullptr) {
+  static_assert(!ACCUM || !RECOVER, "accumulate is the encode form: no packet is skipped");
   f.p0 = a.grp_ptr[g];
   f.k = a.grp_ptr[g + 1] - f.p0;
   f.m = 0xFFFFFFFFu;
   f.plen = 0;
-  if constexpr (RECOVER) {
+  if constexpr (ACCUM) {
+    const uint32_t s = x->slot ? x->slot[g] : x->slot_base + (uint32_t)g;
+    f.slot = s;
+    f.old = s < x->n_slots ? (uint32_t)x->acc_len[s] : kAccBadSlot;
+    f.dst_off = (uint64_t)s * x->acc_stride;
+  } else if constexpr (RECOVER) {
     if constexpr (LIST) f.m = list_m;
     else f.m = a.missing[g];
     f.plen = a.parity_len[g];
@@ -1160,14 +1180,18 @@ __device__ __forceinline__ void group_scalars(const RaggedArgs& a, uint64_t g, G
 }
 
 // Vector part (needs the scalars).  Invalid groups load nothing.
-template <bool RECOVER, bool NT>
+// ACCUM: the slot's row up to its old length is the "parity row"; a fresh slot
+// (old == 0) loads nothing of it.
+template <bool RECOVER, bool NT, bool ACCUM = false>
 __device__ __forceinline__ void group_vectors(const RaggedArgs& a, uint64_t g, uint32_t lane,
-                                              GroupPrefetch& f) {
+                                              GroupPrefetch& f,
+                                              const AccumulateRaggedArgs* x = nullptr) {
   f.len = f.offlo = f.offhi = 0;
   const u32x4 zero = {0u, 0u, 0u, 0u};
   f.pw0 = f.pw1 = zero;
-  const bool ok = f.k >= 1u && f.k <= 255u && (!RECOVER || (f.m < f.k && f.plen >= 1u &&
-                                                             f.plen <= kMaxPacket));
+  bool ok = f.k >= 1u && f.k <= 255u && (!RECOVER || (f.m < f.k && f.plen >= 1u &&
+                                                       f.plen <= kMaxPacket));
+  if constexpr (ACCUM) ok = ok && f.old <= x->lim;  // (kAccBadSlot is above any limit)
   if (!ok) return;
   const uint32_t kr = RECOVER ? f.k - 1u : f.k;
   if (lane < kr) {
@@ -1182,21 +1206,50 @@ __device__ __forceinline__ void group_vectors(const RaggedArgs& a, uint64_t g, u
     if (16u * lane < f.plen) f.pw0 = packet_window<NT>(prow, f.plen, lane);
     if (16u * (lane + 64u) < f.plen) f.pw1 = packet_window<NT>(prow, f.plen, lane + 64u);
   }
+  if constexpr (ACCUM) {
+    const uint8_t* prow = a.parity + f.dst_off;
+    if (16u * lane < f.old) f.pw0 = packet_window<NT>(prow, f.old, lane);
+    if (16u * (lane + 64u) < f.old) f.pw1 = packet_window<NT>(prow, f.old, lane + 64u);
+  }
 }
 
 // One group, one wave (see the flat-window description above).
-template <bool RECOVER, bool NT, int U, int ACC, bool BF = false>
+//
+// ACCUM (qfec_accumulate_ragged, x its arguments): the encode form whose
+// accumulator starts from the slot's own row (zero from its old length on) and
+// whose output goes back to that row, its length the running maximum.  In
+// place is safe because every load of the row precedes every store to it: the
+// row is read only by the prefetch (group_vectors), whose windows are in LDS
+// before the first store below, and the unaligned tail store ("the 16 bytes
+// ending at the length") overlaps the previous window's store with identical
+// bytes.  A group that latches an error returns before any store, to the row
+// or to its length; a group of no packets is a no-op.
+template <bool RECOVER, bool NT, int U, int ACC, bool BF = false, bool ACCUM = false>
 __device__ __forceinline__ void ragged_group(const RaggedArgs& a, uint64_t g, uint32_t lane,
                                              const GroupPrefetch& f, uint32_t* par,
-                                             uint64_t* head, u32x4* meta) {
+                                             uint64_t* head, u32x4* meta,
+                                             const AccumulateRaggedArgs* x = nullptr) {
   const uint32_t p0 = f.p0, k = f.k, m = f.m;
   uint32_t plen = f.plen;
-  if (k == 0u || k > 255u) {  // grp_ptr not monotone shows up as k > 255 too
+  if ((!ACCUM && k == 0u) || k > 255u) {  // grp_ptr not monotone shows up as k > 255 too
     if (lane == 0) atomicOr(a.err, kErrGroupSize);
     return;
   }
   const u32x4 zero = {0u, 0u, 0u, 0u};
-  if constexpr (RECOVER) {
+  if constexpr (ACCUM) {
+    if (f.old == kAccBadSlot) {  // slot >= n_slots
+      if (lane == 0) atomicOr(a.err, kErrMissingIndex);
+      return;
+    }
+    if (f.old > x->lim) {
+      if (lane == 0) atomicOr(a.err, kErrParityLength);
+      return;
+    }
+    if (k == 0u) return;  // nothing to fold this turn
+    // accumulator := the slot's row (zero from its old length on)
+    lds_put16<ACC>(par, lane, f.pw0);
+    if (lane + 64u < kParWin) lds_put16<ACC>(par, lane + 64u, f.pw1);
+  } else if constexpr (RECOVER) {
     if (m >= k) {
       if (lane == 0) atomicOr(a.err, kErrMissingIndex);
       return;
@@ -1212,7 +1265,8 @@ __device__ __forceinline__ void ragged_group(const RaggedArgs& a, uint64_t g, ui
     for (uint32_t t = lane; t < kParWin; t += 64u) lds_put16<ACC>(par, t, zero);
   }
   const uint32_t kr = RECOVER ? k - 1u : k;  // received packets
-  const uint32_t lim = RECOVER ? plen : kMaxPacket;
+  uint32_t lim = RECOVER ? plen : kMaxPacket;
+  if constexpr (ACCUM) lim = x->lim;
   uint32_t mx = 0;
   for (uint32_t c = 0; c < kr; c += 64u) {
     // packet table of this chunk: lane j = received packet c + j
@@ -1341,7 +1395,10 @@ __device__ __forceinline__ void ragged_group(const RaggedArgs& a, uint64_t g, ui
       }
     }
   }
-  if constexpr (!RECOVER) {
+  if constexpr (ACCUM) {
+    plen = max(wave_max11(mx), f.old);
+    if (lane == 0) x->acc_len[f.slot] = (uint16_t)plen;
+  } else if constexpr (!RECOVER) {
     plen = wave_max11(mx);
     if (lane == 0) a.parity_len_out[g] = (uint16_t)plen;
   }
@@ -1424,13 +1481,32 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t lane, u
 // slots below the count are ever turned into a group.  Every return of the
 // body is block-uniform, so a kernel may call it once per list step with a
 // barrier between the steps (revive_ragged_kernel).
+// ACCUM (encode form, qfec_accumulate_ragged; x its arguments): group slot j
+// folds into accumulator row s = slot[g] (or g) of the caller's buffer, in
+// place.  The LDS accumulator starts from that row up to its OLD length
+// (s_old, zero from there on; nothing is loaded for a fresh slot, old == 0),
+// the packets' lengths are limited by x->lim as in an encode, and the NEW
+// length -- s_pl, which starts at the old one and takes the atomicMax of the
+// packet lengths -- is written back to acc_len[s].  Two values on purpose: the
+// row preload below reads the length with no barrier before the atomicMax.
+// In place is safe because every load of a row precedes every store to it:
+// the rows are read only by the preload, whose windows are in LDS before the
+// barriers that follow it, and stored only after the last barrier; the
+// unaligned tail store ("the 16 bytes ending at the length") overlaps the
+// previous window's store with identical bytes.  Steps the block path does
+// not take (an old length of 1..15, a group of no packets, any invalid field,
+// and the cases above) run the per-group body, which leaves the row and the
+// length of a group it rejects untouched.
 template <bool RECOVER, int WAVES, int GPB, int U = 2, bool PF = true, bool AL = true, int DIAG = 0,
-          bool LIST = false>
+          bool LIST = false, bool ACCUM = false>
 __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
                                                   const uint64_t* __restrict__ work = nullptr,
-                                                  uint64_t count = 0, uint64_t step = 0) {
+                                                  uint64_t count = 0, uint64_t step = 0,
+                                                  const AccumulateRaggedArgs* x = nullptr) {
   static_assert(GPB >= 2 && GPB <= 64, "group slots are lanes of wave 0");
   static_assert(!LIST || RECOVER, "the work list is a receiver's");
+  static_assert(!ACCUM || (!RECOVER && !LIST && PF), "accumulate: the encode form, preloaded");
+  constexpr bool ROWIN = RECOVER || ACCUM;  // the accumulators start from a row
   constexpr uint32_t NT = 64u * WAVES;
   constexpr uint32_t NBLK = NT;        // 64-window blocks: CAPW = 64 NT windows
   constexpr uint32_t CAPW = 64u * NBLK;
@@ -1444,6 +1520,7 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
   __shared__ uint32_t s_rb[GPB + 1], s_kb[GPB], s_m[GPB], s_pl[GPB], s_ob[GPB + 1];
   __shared__ uint64_t s_doff[GPB], s_poff[GPB];
   __shared__ uint32_t s_w[WAVES], s_fit;
+  __shared__ uint32_t s_old[GPB], s_slot[GPB];  // ACCUM only (else never referenced)
   uint32_t* acc = s_raw;
   u32x4* pk = reinterpret_cast<u32x4*>(s_raw + GPB * kAccWords);
   const uint32_t tid = threadIdx.x;
@@ -1465,7 +1542,15 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
       if constexpr (LIST) list_entry(work[g0 + lane], g, m);
       p0 = a.grp_ptr[g];
       k = a.grp_ptr[g + 1] - p0;
-      if constexpr (RECOVER) {
+      if constexpr (ACCUM) {
+        const uint32_t s = x->slot ? x->slot[g] : x->slot_base + (uint32_t)g;
+        const bool sok = s < x->n_slots;
+        pl = sok ? (uint32_t)x->acc_len[s] : 0u;  // the old length
+        d = po = (uint64_t)s * x->acc_stride;
+        ok = sok && pl <= x->lim && (pl == 0u || pl >= 16u);
+        s_slot[lane] = s;
+        s_old[lane] = pl;
+      } else if constexpr (RECOVER) {
         if constexpr (!LIST) m = a.missing[g0 + lane];
         pl = a.parity_len[g];
         d = a.out_off[g];
@@ -1497,11 +1582,17 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
   const uint32_t R = s_rb[GPB];
   bool fit = s_fit != 0u;
   // ---- 2. one received packet per lane
-  if (RECOVER && PF && fit) {
+  if (ROWIN && PF && fit) {
     for (uint32_t q = tid; q < GPB * (uint32_t)kParWin; q += NT) {
       const uint32_t jq = q / (uint32_t)kParWin, t = q - jq * (uint32_t)kParWin;
       u32x4 w = {0u, 0u, 0u, 0u};
-      if (jq < ng) w = parity_window_bf<true>(a.parity + s_poff[jq], s_pl[jq], t);
+      if constexpr (ACCUM) {
+        // (s_old, not s_pl: the atomicMax below may already have raised that)
+        if (jq < ng && s_old[jq] != 0u)
+          w = parity_window_bf<true>(a.parity + s_poff[jq], s_old[jq], t);
+      } else {
+        if (jq < ng) w = parity_window_bf<true>(a.parity + s_poff[jq], s_pl[jq], t);
+      }
       lds_put16<1>(acc + jq * kAccWords, t, w);
     }
   }
@@ -1515,7 +1606,9 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
     const uint64_t o = a.pkt_off[p];
     offlo = (uint32_t)o;
     offhi = (uint32_t)(o >> 32);
-    const uint32_t lim = RECOVER ? s_pl[j] : kMaxPacket;
+    uint32_t lim = kMaxPacket;
+    if constexpr (RECOVER) lim = s_pl[j];
+    if constexpr (ACCUM) lim = x->lim;
     if (len < 16u || len > lim) s_fit = 0u;  // benign race: every writer stores 0
     if (!RECOVER) atomicMax(&s_pl[j], len);
   }
@@ -1531,12 +1624,12 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
       uint64_t g = g0 + jj;
       uint32_t lm = 0;
       if constexpr (LIST) list_entry(work[g0 + jj], g, lm);  // jj < ng: below the count
-      group_scalars<RECOVER, LIST>(a, g, f, lm);
-      group_vectors<RECOVER, true>(a, g, lane, f);
+      group_scalars<RECOVER, LIST, ACCUM>(a, g, f, lm, x);
+      group_vectors<RECOVER, true, ACCUM>(a, g, lane, f, x);
       wave_lds_order();
-      ragged_group<RECOVER, true, 2, 1>(a, g, lane, f, fb,
-                                        reinterpret_cast<uint64_t*>(fb + 4u * kParWin),
-                                        reinterpret_cast<u32x4*>(fb + 6u * kParWin));
+      ragged_group<RECOVER, true, 2, 1, false, ACCUM>(
+          a, g, lane, f, fb, reinterpret_cast<uint64_t*>(fb + 4u * kParWin),
+          reinterpret_cast<u32x4*>(fb + 6u * kParWin), x);
       wave_lds_order();
     }
     return;
@@ -1547,7 +1640,7 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
                           __HIP_MEMORY_SCOPE_WORKGROUP);
   }
   // accumulators: the parity rows (recover) or zero (encode), windows of all groups
-  if (!(RECOVER && PF)) {
+  if (!(ROWIN && PF)) {
     for (uint32_t q = tid; q < GPB * (uint32_t)kParWin; q += NT) {
       const uint32_t jq = q / (uint32_t)kParWin, t = q - jq * (uint32_t)kParWin;
       u32x4 w = {0u, 0u, 0u, 0u};
@@ -1569,7 +1662,11 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
     const uint32_t incl = wave_incl_scan(nw, lane);
     if (lane < (uint32_t)GPB) s_ob[lane] = incl - nw;
     if (lane == 0u) s_ob[GPB] = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    if (!RECOVER && lane < ng) a.parity_len_out[g0 + lane] = (uint16_t)s_pl[lane];
+    if constexpr (ACCUM) {
+      if (lane < ng) x->acc_len[s_slot[lane]] = (uint16_t)s_pl[lane];
+    } else {
+      if (!RECOVER && lane < ng) a.parity_len_out[g0 + lane] = (uint16_t)s_pl[lane];
+    }
   }
   __syncthreads();
   // ---- 3. the flat windows, U iterations' loads in flight
@@ -1714,6 +1811,23 @@ __global__ __launch_bounds__(64 * WAVES) void revive_ragged_kernel(
     ragged_block_body<true, WAVES, GPB, 2, true, true, 0, true>(a, work, count, step);
     __syncthreads();  // the step's LDS reads are done before the next step's writes
   }
+}
+
+// qfec_accumulate_ragged: the encode block body in its accumulate mode, GPB
+// groups per block.  The accumulator buffer is both the body's "parity" (the
+// rows on entry) and its output.
+template <int WAVES, int GPB>
+__global__ __launch_bounds__(64 * WAVES) void accumulate_ragged_kernel(AccumulateRaggedArgs v) {
+  RaggedArgs a{};
+  a.bytes = v.bytes;
+  a.pkt_off = v.pkt_off;
+  a.pkt_len = v.pkt_len;
+  a.grp_ptr = v.grp_ptr;
+  a.parity = v.acc;
+  a.out = v.acc;
+  a.n_groups = v.n_groups;
+  a.err = v.err;
+  ragged_block_body<false, WAVES, GPB, 2, true, true, 0, false, true>(a, nullptr, 0, 0, &v);
 }
 
 
@@ -3043,6 +3157,25 @@ hipError_t launch_revive_ragged(const ReviveRaggedArgs& a, hipStream_t s) {
                      dim3((uint32_t)std::min(steps, resident)), dim3(64 * kRaggedBlockWaves), 0, s,
                      a, a.work, a.totals);
   return hipGetLastError();
+}
+
+hipError_t launch_accumulate_ragged(const AccumulateRaggedArgs& a0, hipStream_t s) {
+  if (a0.n_groups == 0) return hipSuccess;
+  const uint64_t gpb = kRaggedBlockGroups;
+  const uint64_t maxg = kMaxBlocks256 * gpb;
+  for (uint64_t g = 0; g < a0.n_groups; g += maxg) {
+    AccumulateRaggedArgs a = a0;
+    a.n_groups = std::min<uint64_t>(maxg, a0.n_groups - g);
+    a.grp_ptr = a0.grp_ptr + g;
+    if (a0.slot) a.slot = a0.slot + g;
+    else a.slot_base = (uint32_t)g;
+    const uint64_t blocks = (a.n_groups + gpb - 1) / gpb;
+    hipLaunchKernelGGL((accumulate_ragged_kernel<kRaggedBlockWaves, kRaggedBlockGroups>),
+                       dim3((uint32_t)blocks), dim3(64 * kRaggedBlockWaves), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_ragged(const RaggedArgs& a0, bool recover, hipStream_t s, bool small_groups) {

@@ -81,6 +81,8 @@ SIGNATURES = [
       _u8p, _vp, _vp, C.c_uint32]),
     ("qfec_recover_ragged", C.c_int,
      [_vp, _u8p, _vp, _vp, _vp, C.c_uint64, _u8p, _vp, _vp, _u8p, _u8p, _vp, C.c_uint32]),
+    ("qfec_accumulate_ragged", C.c_int,
+     [_vp, _u8p, _vp, _vp, _vp, C.c_uint64, _u8p, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint32]),
     ("qfec_xor_into", C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint32]),
     ("qfec_wire_write_private_header", C.c_size_t, [_vp, _u8p, C.c_size_t]),
     ("qfec_wire_parse_private_header", C.c_size_t,
@@ -455,6 +457,19 @@ class Context:
                                          _ptr(parity_off), _ptr(parity_len), _ptr(received),
                                          map_stride, _ptr(out), _ptr(out_off), _ptr(status),
                                          _ptr(revived_idx), _ptr(revived_list), _ptr(counts), 0)
+        return self._check(rc)
+
+    def accumulate_ragged(self, data, pkt_off, pkt_len, grp_ptr, n_groups, acc, acc_stride,
+                          acc_len, *, slot=None, n_slots=None):
+        """qfec_accumulate_ragged: fold this turn's packets of every group of a
+        CSR batch into the group's running row acc + s * acc_stride, s =
+        slot[g] (uint32[n]; None: s = g), and raise acc_len[s] (uint16) to the
+        longest packet folded.  n_slots=None: n_groups.  Device pointers only;
+        queued on the context's stream (sync() before reading the results)."""
+        ns = n_groups if n_slots is None else n_slots
+        rc = self.lib.qfec_accumulate_ragged(self.ctx, _ptr(data), _ptr(pkt_off), _ptr(pkt_len),
+                                             _ptr(grp_ptr), n_groups, _ptr(acc), acc_stride,
+                                             _ptr(acc_len), _ptr(slot), ns, 0)
         return self._check(rc)
 
     def xor_into(self, src, n, dst, *, host=False, mapped=False):
