@@ -150,16 +150,22 @@ def test_seal_open_random_vs_oracle(ctx, nkeys, lmax):
 
 
 
-def test_block_shapes_agree_on_large_batch(ctx):
+@pytest.mark.parametrize("lmax", [80, 1452])
+def test_block_shapes_agree_on_large_batch(ctx, lmax):
     """launch_aes128gcm seals batches of >= 2^22 packets with the 768-thread
     shape and smaller ones with the 512-thread shape: the same 2^22 packets
     sealed in one call and in two halves (in place, [header | payload | 12
     spare] records) must give the same bytes, and the (512-thread) open must
-    verify every one of them.  Device-side compare."""
+    verify every one of them.  Device-side compare.  Payloads of 0..80 bytes
+    (at most two of the 768-thread shape's 64-byte slabs) and of 0..1452
+    (every slab count; about 3 GiB a copy).  512 of the packets sealed by the
+    768-thread shape -- the ends of the batch and a spread between -- are
+    copied back and compared with the oracle, so the shape is pinned by the
+    reference and not only by its sibling."""
     n = 1 << 22
     rng = np.random.default_rng(41)
     hdr = 13
-    pt_len = rng.integers(0, 81, n).astype(np.uint16)
+    pt_len = rng.integers(0, lmax + 1, n).astype(np.uint16)
     rec = hdr + pt_len.astype(np.uint64) + TAG
     ad_off = offsets(rec)
     in_off = ad_off + np.uint64(hdr)
@@ -186,6 +192,20 @@ def test_block_shapes_agree_on_large_batch(ctx):
     ctx.sync()
     torch.cuda.synchronize()
     assert torch.equal(whole, halves)
+    sel = np.unique(np.concatenate([np.arange(160), np.arange(n - 160, n),
+                                    np.linspace(160, n - 161, 192).astype(np.int64)]))
+    assert sel.size == 512
+    l = rec[sel].astype(np.int64)
+    idx = torch.from_numpy(np.repeat(ad_off[sel].astype(np.int64) - (np.cumsum(l) - l), l)
+                           + np.arange(int(l.sum()))).to(DEV)
+    before, after = base[idx].cpu().numpy(), whole[idx].cpu().numpy()
+    del idx, halves, base
+    c_ad = offsets(rec[sel])
+    c_in = c_ad + np.uint64(hdr)
+    want = OC.quic_aes128gcm_encrypt_batch(keys, pre, kidx[sel], pn[sel], None, before, c_ad,
+                                           ad_len[sel], c_in, pt_len[sel], c_in, before.size,
+                                           threads=8, out=before.copy())
+    assert np.array_equal(after, want)
     ok = torch.zeros(n, dtype=torch.uint8, device=DEV)
     pout = torch.zeros(int(pt_len.astype(np.int64).sum()) + 1, dtype=torch.uint8, device=DEV)
     ctx.aes128gcm_open(d["keys"], d["pre"], d["kidx"], d["pn"], None, whole, d["ad_off"],
