@@ -19,6 +19,10 @@
  *       is UpdateParity's per-turn form: the packets at hand folded into one
  *       running row per open group (on a receiver Update / UpdateFec as well:
  *       the row is then what Revive() copies out).
+ *   qfec_emit_accumulated / qfec_revive_accumulated
+ *       close such rows: PayloadParity() hands the finished row to the FEC
+ *       packet; NumMissingPackets() + CanRevive() + Revive() decide from the
+ *       receive map and copy the row out as the revived packet.
  *   qfec_recover_batch / _strided / qfec_recover_ragged
  *       replaces QuicFecGroup::UpdateFec + Update(received) + CanRevive() +
  *       Revive().  Receive-side hook: QuicConnection::ProcessValidatedPacket
@@ -426,6 +430,76 @@ int qfec_accumulate_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* 
                            const uint16_t* pkt_len, const uint32_t* grp_ptr, uint64_t n_groups,
                            uint8_t* acc, uint64_t acc_stride, uint16_t* acc_len,
                            const uint32_t* slot, uint64_t n_slots, uint32_t flags);
+
+/* Close running rows: the two exits of qfec_accumulate_ragged.  In both,
+ * group g's row is acc + s * acc_stride with s = slot[g] (slot == NULL: s = g),
+ * len = acc_len[s] and lim = min(1452, acc_stride), exactly as
+ * qfec_accumulate_ragged states them.
+ *
+ * qfec_emit_accumulated is the sender's PayloadParity(), or any "hand me these
+ * rows".  For every group: out_len[g] = len, and len bytes of the row are
+ * copied to out + out_off[g] at any byte alignment (the FEC packet's body
+ * behind its private header).  len == 0 is valid and copies nothing.
+ * release != 0 then sets acc_len[s] = 0: the slot is fresh for the next
+ * qfec_accumulate_ragged.
+ *
+ * qfec_revive_accumulated is the receiver's NumMissingPackets() / CanRevive()
+ * / Revive(), after which the group is deleted.  group_k[g] is the number of
+ * protected packets (1..255); the map of group g is map_stride bytes at
+ * received + g * map_stride, its bits, the rule and the three QFEC_GROUP_*
+ * codes those of qfec_revive_ragged -- the map says which packets HAVE BEEN
+ * FOLDED into the row.  status is required; revived_idx, revived_list
+ * (ascending, not written from the count on) and counts behave as in
+ * qfec_revive_ragged.  A QFEC_GROUP_REVIVED group gets out_len[g] = len and
+ * len bytes of the row at out + out_off[g]: byte for byte what
+ * qfec_recover_ragged writes for the group from its payloads.  out == NULL is
+ * allowed: the revived packet then IS the row, nothing is copied, out_off is
+ * not read and out_len is still written.  Every other group gets
+ * out_len[g] = 0, nothing copied, and its out_off entry is never read.
+ * release_mask: bit st set = groups whose status is st get acc_len[s] = 0
+ * (0b011 closes finished and revived groups and leaves unrevivable ones open
+ * for later packets, 0b111 closes all, 0 none).
+ *
+ * Never read: rows and lengths of slots no group names; row bytes at or beyond
+ * len; rows of groups that are not copied; the map of an invalid group.  Never
+ * written: acc rows, ever; acc_len of slots that are not released; out bytes
+ * outside [out_off[g], out_off[g] + len) of copied groups.
+ * The caller guarantees, unchecked: the slots named in one call are distinct,
+ * out does not overlap acc, and out ranges do not overlap each other.
+ * Latched on the device and returned by the next qfec_sync as
+ * -QUIC_INVALID_FEC_DATA: slot[g] >= n_slots (its acc_len is not read);
+ * group_k[g] == 0 or group_k[g] / 8 + 1 > map_stride; a group to copy with
+ * len > lim; a revived group with len == 0 (the map claims folds the row never
+ * saw).  A group with a bad slot or a bad group_k has status
+ * QFEC_GROUP_UNREVIVABLE and revived_idx 0xFF and is counted as unrevivable;
+ * a revived group with a bad length keeps its status, its place in
+ * revived_list and its count (the status states the map).  Every offending
+ * group gets out_len[g] = 0, nothing copied and no release; every other
+ * group's outputs are right.
+ * Refused on the host (nothing launched, nothing written): acc_stride == 0 or
+ * map_stride == 0 (-QUIC_INVALID_FEC_DATA); QFEC_PTR_HOST, QFEC_PTR_MAPPED or
+ * QFEC_ASYNC; a NULL acc, acc_len or out_len, a NULL out_off when out is
+ * given, for the emit a NULL out, for the revive a NULL group_k, received or
+ * status; n_groups >= 2^32 or n_slots >= 2^32; slot == NULL with
+ * n_slots < n_groups; release_mask > 7 (QFEC_ERR_INTERNAL).  n_groups == 0
+ * succeeds before the buffers are looked at (counts, if given, receives three
+ * zeroes).  QFEC_CACHED and QFEC_SMALL_GROUPS are accepted and change nothing.
+ * Device pointers only; both calls only queue kernels on the context's stream,
+ * never wait and never read anything back, and the revive uses the
+ * context-owned scratch of qfec_revive_batch.  Queued behind a
+ * qfec_accumulate_ragged on one stream they see its rows, and an accumulate
+ * queued behind them sees the released slots as fresh. */
+int qfec_emit_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride,
+                          uint16_t* acc_len, const uint32_t* slot, uint64_t n_slots,
+                          uint64_t n_groups, uint8_t* out, const uint64_t* out_off,
+                          uint16_t* out_len, int release, uint32_t flags);
+int qfec_revive_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride,
+                            uint16_t* acc_len, const uint32_t* slot, uint64_t n_slots,
+                            const uint8_t* group_k, const uint8_t* received, uint64_t map_stride,
+                            uint64_t n_groups, uint8_t* out, const uint64_t* out_off,
+                            uint16_t* out_len, uint8_t* status, uint8_t* revived_idx,
+                            uint64_t* revived_list, uint64_t* counts, uint32_t release_mask,
+                            uint32_t flags);
 
 /* ---- single buffer ------------------------------------------------------ */
 /* out[j] ^= in[j] for j < n (QuicFecGroupInterface::XorBuffers). */

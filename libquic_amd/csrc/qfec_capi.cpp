@@ -2157,6 +2157,131 @@ int qfec_accumulate_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* 
   return QFEC_OK;
 }
 
+namespace {
+
+// The host checks the two closing calls share (what: the call's name in the
+// messages); QFEC_OK: launch.
+int close_check(qfec_ctx* ctx, const char* what, uint64_t n_slots, uint64_t n_groups,
+                const uint32_t* slot, uint32_t flags) {
+  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: device pointers only, queued on the context's stream (QFEC_PTR_HOST, "
+                "QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)", what);
+  if (n_groups >= (1ull << 32) || n_slots >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: 2^32 or more groups or slots (group and slot indices are 32 bits)", what);
+  if (!slot && n_slots < n_groups)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: slot == NULL closes slot g for group g, and there are fewer slots than "
+                "groups", what);
+  return QFEC_OK;
+}
+
+}  // namespace
+
+// QuicFecGroup::PayloadParity for running rows: one gather launch, which also
+// writes the lengths and releases the slots.
+int qfec_emit_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride,
+                          uint16_t* acc_len, const uint32_t* slot, uint64_t n_slots,
+                          uint64_t n_groups, uint8_t* out, const uint64_t* out_off,
+                          uint16_t* out_len, int release, uint32_t flags) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  ctx->last_ticket = 0;
+  if (ctx->debug_fail)
+    return fail(ctx, QFEC_ERR_INTERNAL, "launch failure injected (qfec_debug_fail_launches)");
+  if (acc_stride == 0)
+    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+                "accumulator stride 0: a row holds the longest packet folded into it");
+  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
+    return close_check(ctx, "emit accumulated", n_slots, n_groups, slot, flags);
+  if (n_groups == 0) return QFEC_OK;
+  if (!acc || !acc_len || !out || !out_off || !out_len)
+    return fail(ctx, QFEC_ERR_INTERNAL, "emit accumulated: null buffer (only slot may be NULL)");
+  if ((rc = close_check(ctx, "emit accumulated", n_slots, n_groups, slot, flags)))
+    return rc;
+  qfec::CloseArgs a{};
+  a.acc = acc;
+  a.acc_stride = acc_stride;
+  a.acc_len = acc_len;
+  a.slot = slot;
+  a.n_groups = n_groups;
+  a.out = out;
+  a.out_off = out_off;
+  a.out_len = out_len;
+  a.err = ctx->d_err;
+  a.n_slots = (uint32_t)n_slots;
+  a.lim = (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
+  a.release = release != 0 ? 1u : 0u;
+  a.ncu = ctx->ncu;
+  QFEC_HIP(ctx, qfec::launch_close_emit(a, ctx->stream));
+  return QFEC_OK;
+}
+
+// The receiver's close (NumMissingPackets / CanRevive / Revive, then the
+// group is deleted) for running rows: classify / scan / emit as the other
+// revives, sharing their scratch, then the gather over the work list.
+int qfec_revive_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride,
+                            uint16_t* acc_len, const uint32_t* slot, uint64_t n_slots,
+                            const uint8_t* group_k, const uint8_t* received, uint64_t map_stride,
+                            uint64_t n_groups, uint8_t* out, const uint64_t* out_off,
+                            uint16_t* out_len, uint8_t* status, uint8_t* revived_idx,
+                            uint64_t* revived_list, uint64_t* counts, uint32_t release_mask,
+                            uint32_t flags) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  ctx->last_ticket = 0;
+  if (ctx->debug_fail)
+    return fail(ctx, QFEC_ERR_INTERNAL, "launch failure injected (qfec_debug_fail_launches)");
+  if (acc_stride == 0)
+    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+                "accumulator stride 0: a row holds the longest packet folded into it");
+  if (map_stride == 0)
+    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+                "receive map stride 0: a group of k packets needs k / 8 + 1 bytes");
+  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
+    return close_check(ctx, "revive accumulated", n_slots, n_groups, slot, flags);
+  if (release_mask > 7u)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "revive accumulated: release_mask 0x%x has bits above the three group statuses",
+                release_mask);
+  if (n_groups == 0) {
+    if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(uint64_t), ctx->stream));
+    return QFEC_OK;
+  }
+  if (!acc || !acc_len || !group_k || !received || (out && !out_off) || !out_len || !status)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "revive accumulated: null buffer (only slot, out, out_off without out, "
+                "revived_idx, revived_list and counts may be NULL)");
+  if ((rc = close_check(ctx, "revive accumulated", n_slots, n_groups, slot, flags)))
+    return rc;
+  if ((rc = revive_scratch_acquire(ctx, n_groups))) return rc;
+  qfec::CloseArgs a{};
+  a.acc = acc;
+  a.acc_stride = acc_stride;
+  a.acc_len = acc_len;
+  a.slot = slot;
+  a.group_k = group_k;
+  a.received = received;
+  a.map_stride = map_stride;
+  a.n_groups = n_groups;
+  a.out = out;
+  a.out_off = out_off;
+  a.out_len = out_len;
+  a.status = status;
+  a.revived_idx = revived_idx;
+  a.revived_list = revived_list;
+  a.counts = counts;
+  a.err = ctx->d_err;
+  a.n_slots = (uint32_t)n_slots;
+  a.lim = (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
+  a.release = release_mask;
+  a.ncu = ctx->ncu;
+  qfec::revive_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_close_revive(a, ctx->stream));
+  return revive_scratch_release(ctx);
+}
+
 int qfec_xor_into(qfec_ctx* ctx, const uint8_t* in, uint64_t n, uint8_t* out, uint32_t flags) {
   int rc = bind(ctx);
   if (rc) return rc;

@@ -209,6 +209,57 @@ struct AccumulateRaggedArgs {
 // 8 * kMaxBlocks256 groups.  n_groups > 0.
 hipError_t launch_accumulate_ragged(const AccumulateRaggedArgs& a, hipStream_t s);
 
+// Close running rows (qfec_emit_accumulated / qfec_revive_accumulated): group
+// g's row is acc + s * acc_stride of length acc_len[s], s = slot[g] (slot ==
+// nullptr: s = g), as AccumulateRaggedArgs names it.  A struct of its own:
+// ReviveArgs, ReviveRaggedArgs and AccumulateRaggedArgs keep their kernarg
+// layouts.  The emit reads acc .. slot, n_groups, out .. out_len, err, n_slots,
+// lim and release (a flag); the revive all of it (release: bit st set = groups
+// of status st are released).
+// Work-list entry of the revive: g << 8 | m as ReviveRaggedArgs's, and the
+// length to copy (11 bits; 0: copy nothing) from bit kCloseLenShift on -- the
+// pass that releases a slot is the one that captures its length.
+constexpr uint32_t kCloseLenShift = 40;
+struct CloseArgs {
+  const uint8_t* acc;
+  uint64_t acc_stride;
+  uint16_t* acc_len;     // read; zeroed for released slots
+  const uint32_t* slot;  // nullable
+  const uint8_t* group_k;
+  const uint8_t* received;
+  uint64_t map_stride;
+  uint64_t n_groups;  // < 2^32
+  uint8_t* out;       // revive: nullable (the revived packet is the row)
+  const uint64_t* out_off;
+  uint16_t* out_len;
+  uint8_t* status;
+  uint8_t* revived_idx;    // nullable
+  uint64_t* revived_list;  // nullable
+  uint64_t* counts;        // nullable: [complete, revived, unrevivable]
+  // scratch, as ReviveArgs (revive_scratch_bytes(n_groups))
+  uint32_t* tile_cnt;
+  uint64_t* tile_off;
+  uint64_t* totals;
+  uint64_t* work;
+  uint32_t* err;
+  uint32_t n_slots;
+  uint32_t lim;  // min(kMaxPacket, acc_stride): longest row
+  uint32_t release;
+  uint32_t ncu;
+};
+inline void revive_scratch_layout(CloseArgs& a, void* block) {
+  uint8_t* p = static_cast<uint8_t*>(block);
+  a.totals = reinterpret_cast<uint64_t*>(p);
+  a.work = reinterpret_cast<uint64_t*>(p + 32);
+  a.tile_off = a.work + a.n_groups + kReviveListPad;
+  a.tile_cnt = reinterpret_cast<uint32_t*>(a.tile_off + revive_tiles(a.n_groups));
+}
+// One launch on s: the gather over every group.  n_groups > 0.
+hipError_t launch_close_emit(const CloseArgs& a, hipStream_t s);
+// Four launches on s (classify, scan, emit, the gather over the work list;
+// three when out == nullptr), ordered by the stream alone.  n_groups > 0.
+hipError_t launch_close_revive(const CloseArgs& a, hipStream_t s);
+
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch
 // per batch (the launch is most of a small flush's connection-thread cost).

@@ -42,6 +42,11 @@
 //    third mode beside encode and recover -- the accumulators start from the
 //    caller's rows (zero past their old lengths) and are stored back in place,
 //    the lengths the running maxima (accumulate_ragged_kernel).
+//  * Closing those rows (qfec_emit_accumulated / qfec_revive_accumulated): a
+//    gather, one wave per row, chunks cut where the destination is 16-B
+//    aligned (close_gather_kernel) -- over every group for the emit, over the
+//    revive's work list (classify / scan / emit with k per group from group_k)
+//    for the receiver's close.
 #include "qfec_internal.h"
 
 #include <algorithm>
@@ -756,9 +761,62 @@ __device__ __forceinline__ bool revive_group_k(const ReviveRaggedArgs& a, uint64
   k = a.grp_ptr[g + 1] - a.grp_ptr[g];  // a non-monotone grp_ptr shows up as k > 255
   return k >= 1u && k <= 255u && (uint64_t)(k / 8u + 1u) <= a.map_stride;
 }
-__device__ __forceinline__ void revive_bad_group(const ReviveArgs&) {}
-__device__ __forceinline__ void revive_bad_group(const ReviveRaggedArgs& a) {
+__device__ __forceinline__ void revive_bad_group(const ReviveArgs&, uint64_t) {}
+__device__ __forceinline__ void revive_bad_group(const ReviveRaggedArgs& a, uint64_t) {
   atomicOr(a.err, kErrGroupSize);
+}
+// The EMIT pass's look at every group of the batch (st 3: past it); returns
+// bits to OR into a revived group's work-list entry.  Nothing for the two
+// revives above.
+__device__ __forceinline__ uint64_t revive_emit_group(const ReviveArgs&, uint64_t, uint32_t) {
+  return 0ull;
+}
+__device__ __forceinline__ uint64_t revive_emit_group(const ReviveRaggedArgs&, uint64_t,
+                                                      uint32_t) {
+  return 0ull;
+}
+
+// CloseArgs (qfec_revive_accumulated): k per group from group_k; a group whose
+// slot is out of range (kErrMissingIndex), whose k is 0 or whose k + 1 bits do
+// not fit map_stride (kErrGroupSize) is unrevivable -- its map and its slot's
+// length are not read.
+__device__ __forceinline__ uint32_t close_slot(const CloseArgs& a, uint64_t g) {
+  return a.slot ? a.slot[g] : (uint32_t)g;
+}
+__device__ __forceinline__ bool close_k_ok(const CloseArgs& a, uint32_t k) {
+  return k >= 1u && (uint64_t)(k / 8u + 1u) <= a.map_stride;
+}
+__device__ __forceinline__ bool revive_group_k(const CloseArgs& a, uint64_t g, uint32_t& k) {
+  k = a.group_k[g];
+  return close_slot(a, g) < a.n_slots && close_k_ok(a, k);
+}
+__device__ __forceinline__ void revive_bad_group(const CloseArgs& a, uint64_t g) {
+  if (close_slot(a, g) >= a.n_slots) atomicOr(a.err, kErrMissingIndex);
+  if (!close_k_ok(a, a.group_k[g])) atomicOr(a.err, kErrGroupSize);
+}
+// out_len and the release, one lane per group: a revived group's length is
+// read here, ONCE, and travels in its work-list entry (the gather never reads
+// acc_len), so the zero stored below cannot reach the copy.  A revived group
+// whose length is 0 or above the limit latches kErrParityLength: out_len 0,
+// entry length 0 (nothing copied), no release.  Invalid groups: out_len 0, no
+// release.
+__device__ __forceinline__ uint64_t revive_emit_group(const CloseArgs& a, uint64_t g,
+                                                      uint32_t st) {
+  if (st > kGroupUnrevivable) return 0ull;
+  const uint32_t s = close_slot(a, g);
+  uint32_t len = 0;
+  if (s < a.n_slots && close_k_ok(a, a.group_k[g])) {
+    bool ok = true;
+    if (st == kGroupRevived) {
+      const uint32_t l = a.acc_len[s];
+      ok = l >= 1u && l <= a.lim;
+      if (ok) len = l;
+      else atomicOr(a.err, kErrParityLength);
+    }
+    if (ok && ((a.release >> st) & 1u) != 0u) a.acc_len[s] = 0;
+  }
+  a.out_len[g] = (uint16_t)len;
+  return (uint64_t)len << kCloseLenShift;
 }
 
 template <bool EMIT, typename Args>
@@ -775,7 +833,7 @@ __global__ __launch_bounds__(kReviveTile) void revive_classify_kernel(Args a) {
         st = revive_classify(a.received + g * a.map_stride, k, m);
       } else {
         st = kGroupUnrevivable;
-        if constexpr (!EMIT) revive_bad_group(a);
+        if constexpr (!EMIT) revive_bad_group(a, g);
       }
     }
     const uint64_t brev = __ballot(st == kGroupRevived);
@@ -791,12 +849,13 @@ __global__ __launch_bounds__(kReviveTile) void revive_classify_kernel(Args a) {
     } else {
       if (lane == 0u) s_w[wave] = (uint32_t)__popcll(brev);
       __syncthreads();
+      const uint64_t ex = revive_emit_group(a, g, st);
       if (st == kGroupRevived) {
         uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(brev >> 32),
                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)brev, 0u));
         for (uint32_t w = 0; w < wave; ++w) rank += s_w[w];
         const uint64_t pos = a.tile_off[tile] + rank;
-        a.work[pos] = (g << 8) | m;
+        a.work[pos] = (g << 8) | m | ex;
         if (a.revived_list) a.revived_list[pos] = g;
       }
     }
@@ -1830,6 +1889,112 @@ __global__ __launch_bounds__(64 * WAVES) void accumulate_ragged_kernel(Accumulat
   ragged_block_body<false, WAVES, GPB, 2, true, true, 0, false, true>(a, nullptr, 0, 0, &v);
 }
 
+// Lane j's 64-bit value as a scalar (j wave-uniform).
+__device__ __forceinline__ uint64_t lane_get64(uint64_t v, uint32_t j) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)j);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)j);
+  return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+
+// qfec_emit_accumulated (LIST = false: every group, the call's one launch) and
+// qfec_revive_accumulated's fourth kernel (LIST = true: the work list, its
+// count read from scratch as revive_xor_kernel reads it): copy len bytes of
+// row acc + s * acc_stride to out + out_off[g], one wave per row.
+// A wave takes `per` consecutive rows at a time -- the rows spread evenly over
+// the grid's waves, 64 at most -- and lane j fetches row j's tables (entry or
+// group, slot, length, out_off) for all of them at once, so the dependent
+// chain entry -> slot -> length in front of a row's bytes is paid once per
+// step, not once per row; the rows are then copied one by one with the lane's
+// values read back as scalars (v_readlane).  LIST = false does its bookkeeping
+// in that per-lane part: out_len, a slot out of range (kErrMissingIndex) or a
+// length above the limit (kErrParityLength; both: out_len 0, nothing copied,
+// no release) and, with release, acc_len[s] = 0 -- stored after the lane's
+// own load of it, and the copy reads the length from the lane, never from
+// acc_len.  out_off is read only for rows that are copied.
+// A row of 16 bytes or more is cut where the DESTINATION is 16-B aligned (a
+// 16-B store across a 16-B boundary costs two): with h
+// the bytes up to dst's first boundary, the aligned chunks [h + 16 t,
+// h + 16 t + 16), the head [0, 16) if h != 0 and the tail, the 16 bytes ending
+// at the length, if the chunks do not end there.  Head and tail overlap their
+// neighbours with identical bytes; every chunk lies inside [0, len) of both
+// the row and the destination.  At most 90 + 2 chunks (len <= 1452): two per
+// lane, both loads issued before the first store; a chunk number past the
+// last one loads the tail again and stores nothing.  Shorter rows go a byte
+// per lane.
+template <bool LIST>
+__global__ __launch_bounds__(kBlock) void close_gather_kernel(CloseArgs a,
+                                                              const uint64_t* __restrict__ work,
+                                                              const uint64_t* __restrict__ totals) {
+  constexpr uint32_t kWaves = kBlock / 64;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // (n_groups < 2^32, so the counts and the divisions are 32-bit)
+  uint32_t count = (uint32_t)a.n_groups;
+  if constexpr (LIST) count = (uint32_t)totals[kGroupRevived];
+  if (count == 0u) return;
+  const uint32_t nwave = gridDim.x * kWaves;
+  const uint32_t per = min(count / nwave + (count % nwave != 0u ? 1u : 0u), 64u);
+  const uint32_t nstep = count / per + (count % per != 0u ? 1u : 0u);
+  for (uint32_t step = blockIdx.x * kWaves + wave; step < nstep; step += nwave) {
+    const uint64_t i = (uint64_t)step * per + lane;
+    uint32_t len = 0;
+    uint64_t soff = 0, doff = 0;
+    if (lane < per && i < (uint64_t)count) {
+      uint64_t g;
+      uint32_t s;
+      if constexpr (LIST) {
+        const uint64_t e = work[i];
+        uint32_t m;
+        list_entry(e, g, m);
+        len = ((uint32_t)(e >> 32) >> (kCloseLenShift - 32u)) & 0x7FFu;
+        s = close_slot(a, g);  // in range: the emit pass gave the entry a length
+      } else {
+        g = i;
+        s = close_slot(a, g);
+        uint32_t bad = s >= a.n_slots ? kErrMissingIndex : 0u;
+        if (bad == 0u) {
+          len = a.acc_len[s];
+          if (len > a.lim) {
+            bad = kErrParityLength;
+            len = 0;
+          }
+        }
+        a.out_len[g] = (uint16_t)len;
+        if (bad != 0u) atomicOr(a.err, bad);
+        else if (a.release != 0u) a.acc_len[s] = 0;
+      }
+      if (len != 0u) {
+        soff = (uint64_t)s * a.acc_stride;
+        doff = a.out_off[g];
+      }
+    }
+    for (uint64_t todo = __ballot(len != 0u); todo != 0ull; todo &= todo - 1ull) {
+      const uint32_t j = (uint32_t)__builtin_ctzll(todo);
+      const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)len, (int)j);
+      const uint8_t* src = a.acc + lane_get64(soff, j);
+      uint8_t* dst = a.out + lane_get64(doff, j);
+      if (n >= 16u) {
+        const uint32_t h = (0u - (uint32_t)reinterpret_cast<uintptr_t>(dst)) & 15u;
+        const uint32_t na = (n - h) >> 4;
+        const bool tail = h + 16u * na != n;
+        uint32_t o[2];
+        bool st[2];
+#pragma unroll
+        for (uint32_t c = 0; c < 2u; ++c) {
+          const uint32_t t = lane + 64u * c;
+          o[c] = t < na ? h + 16u * t : t == na ? 0u : n - 16u;
+          st[c] = t < na || (t == na ? h != 0u : (t == na + 1u && tail));
+        }
+        const u32x4 v0 = ld16t<true>(src + o[0]), v1 = ld16t<true>(src + o[1]);
+        if (st[0]) st16t<true>(dst + o[0], v0);
+        if (st[1]) st16t<true>(dst + o[1], v1);
+      } else if (lane < n) {
+        dst[lane] = src[lane];
+      }
+    }
+  }
+}
+static_assert((kMaxPacket + 15u) / 16u + 2u <= 128u, "two chunks per lane cover a row");
 
 // Two groups per wave (round 2's product kernel; since round 6 the kernel of
 // large batches whose groups are small -- launch_ragged's shape-aware choice,
@@ -3156,6 +3321,39 @@ hipError_t launch_revive_ragged(const ReviveRaggedArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((revive_ragged_kernel<kRaggedBlockWaves, kRaggedBlockGroups>),
                      dim3((uint32_t)std::min(steps, resident)), dim3(64 * kRaggedBlockWaves), 0, s,
                      a, a.work, a.totals);
+  return hipGetLastError();
+}
+
+// The gather's grid: its waves loop over the rows, eight workgroups per CU
+// (every wave slot) or one wave per row, whichever is smaller.
+static uint32_t close_gather_grid(const CloseArgs& a) {
+  const uint64_t blocks = (a.n_groups + kBlock / 64 - 1) / (kBlock / 64);
+  return (uint32_t)std::min<uint64_t>(blocks, (uint64_t)(a.ncu ? a.ncu : 256u) * 8u);
+}
+
+hipError_t launch_close_emit(const CloseArgs& a, hipStream_t s) {
+  if (a.n_groups == 0) return hipSuccess;
+  hipLaunchKernelGGL(close_gather_kernel<false>, dim3(close_gather_grid(a)), dim3(kBlock), 0, s, a,
+                     nullptr, nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_close_revive(const CloseArgs& a, hipStream_t s) {
+  if (a.n_groups == 0) return hipSuccess;
+  const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
+  hipLaunchKernelGGL((revive_classify_kernel<false, CloseArgs>), dim3(cgrid), dim3(kReviveTile), 0,
+                     s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(revive_scan_kernel<CloseArgs>, dim3(1), dim3(kRvScanBlock), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL((revive_classify_kernel<true, CloseArgs>), dim3(cgrid), dim3(kReviveTile), 0,
+                     s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (!a.out) return hipSuccess;  // the revived packets are the rows
+  // the count stays on the device: the grid is sized by the worst case
+  hipLaunchKernelGGL(close_gather_kernel<true>, dim3(close_gather_grid(a)), dim3(kBlock), 0, s, a,
+                     a.work, a.totals);
   return hipGetLastError();
 }
 

@@ -83,6 +83,12 @@ SIGNATURES = [
      [_vp, _u8p, _vp, _vp, _vp, C.c_uint64, _u8p, _vp, _vp, _u8p, _u8p, _vp, C.c_uint32]),
     ("qfec_accumulate_ragged", C.c_int,
      [_vp, _u8p, _vp, _vp, _vp, C.c_uint64, _u8p, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint32]),
+    ("qfec_emit_accumulated", C.c_int,
+     [_vp, _u8p, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint64, _u8p, _vp, _vp, C.c_int,
+      C.c_uint32]),
+    ("qfec_revive_accumulated", C.c_int,
+     [_vp, _u8p, C.c_uint64, _vp, _vp, C.c_uint64, _u8p, _u8p, C.c_uint64, C.c_uint64, _u8p, _vp,
+      _vp, _u8p, _u8p, _vp, _vp, C.c_uint32, C.c_uint32]),
     ("qfec_xor_into", C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint32]),
     ("qfec_wire_write_private_header", C.c_size_t, [_vp, _u8p, C.c_size_t]),
     ("qfec_wire_parse_private_header", C.c_size_t,
@@ -470,6 +476,43 @@ class Context:
         rc = self.lib.qfec_accumulate_ragged(self.ctx, _ptr(data), _ptr(pkt_off), _ptr(pkt_len),
                                              _ptr(grp_ptr), n_groups, _ptr(acc), acc_stride,
                                              _ptr(acc_len), _ptr(slot), ns, 0)
+        return self._check(rc)
+
+    def emit_accumulated(self, acc, acc_stride, acc_len, n_groups, out, out_off, out_len, *,
+                         slot=None, n_slots=None, release=False, flags=0):
+        """qfec_emit_accumulated: copy acc_len[s] bytes of every group's
+        running row acc + s * acc_stride, s = slot[g] (uint32[n]; None: s = g),
+        to out + out_off[g] (uint64[n]) and the length to out_len[g]
+        (uint16[n]); release zeroes acc_len[s] afterwards.  n_slots=None:
+        n_groups.  Device pointers only; queued on the context's stream
+        (sync() before reading the results)."""
+        ns = n_groups if n_slots is None else n_slots
+        rc = self.lib.qfec_emit_accumulated(self.ctx, _ptr(acc), acc_stride, _ptr(acc_len),
+                                            _ptr(slot), ns, n_groups, _ptr(out), _ptr(out_off),
+                                            _ptr(out_len), 1 if release else 0, flags)
+        return self._check(rc)
+
+    def revive_accumulated(self, acc, acc_stride, acc_len, group_k, received, map_stride,
+                           n_groups, out, out_off, out_len, *, status, slot=None, n_slots=None,
+                           revived_idx=None, revived_list=None, counts=None, release_mask=0,
+                           flags=0):
+        """qfec_revive_accumulated: classify every group from its receive map
+        (group_k uint8[n] protected packets; the map says which packets have
+        been folded into the row) and copy the row of the revivable ones to
+        out + out_off[g] (out None: no copy, the row is the packet), its
+        length to out_len[g] (uint16[n]; 0 for every other group).
+        release_mask bit st: groups of status st get acc_len[s] = 0.  status
+        uint8[n]; revived_idx uint8[n], revived_list uint64[n] and counts
+        uint64[3] are optional.  n_slots=None: n_groups.  Device pointers
+        only; queued on the context's stream (sync() before reading the
+        results)."""
+        ns = n_groups if n_slots is None else n_slots
+        rc = self.lib.qfec_revive_accumulated(self.ctx, _ptr(acc), acc_stride, _ptr(acc_len),
+                                              _ptr(slot), ns, _ptr(group_k), _ptr(received),
+                                              map_stride, n_groups, _ptr(out), _ptr(out_off),
+                                              _ptr(out_len), _ptr(status), _ptr(revived_idx),
+                                              _ptr(revived_list), _ptr(counts), release_mask,
+                                              flags)
         return self._check(rc)
 
     def xor_into(self, src, n, dst, *, host=False, mapped=False):
