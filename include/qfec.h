@@ -23,6 +23,10 @@
  *       close such rows: PayloadParity() hands the finished row to the FEC
  *       packet; NumMissingPackets() + CanRevive() + Revive() decide from the
  *       receive map and copy the row out as the revived packet.
+ *   qfec_admit_ragged / qfec_revive_tracked
+ *       keep that receive map (the group's received_packets_) on the device:
+ *       Update()'s duplicate check and the drop of a packet that failed to
+ *       decrypt, before the fold; the close then reads the map by slot.
  *   qfec_recover_batch / _strided / qfec_recover_ragged
  *       replaces QuicFecGroup::UpdateFec + Update(received) + CanRevive() +
  *       Revive().  Receive-side hook: QuicConnection::ProcessValidatedPacket
@@ -500,6 +504,107 @@ int qfec_revive_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stri
                             uint16_t* out_len, uint8_t* status, uint8_t* revived_idx,
                             uint64_t* revived_list, uint64_t* counts, uint32_t release_mask,
                             uint32_t flags);
+
+/* The group's received_packets_ set on the device: one running receive map per
+ * SLOT, consulted before the fold and read by the close.  qfec_revive_accumulated
+ * holds only while the host knows which packets were folded; it does not for a
+ * packet opened on the device, whose verdict ok[p] lies in device memory
+ * (QuicFramer::DecryptPayload drops a packet whose tag fails before the FEC
+ * group sees it), nor for a duplicate (QuicFecGroup::Update returns false for
+ * a packet number already in received_packets_; folded twice it cancels out of
+ * the row).  A receiver's turn is open -> qfec_admit_ragged ->
+ * qfec_accumulate_ragged -> qfec_revive_tracked on one stream, with no sync
+ * and no host decision in between.  The host still assigns slots and
+ * positions (the private flags and the FEC group offset are cleartext).
+ *
+ * qfec_admit_ragged never reads a payload byte.  pkt_off, pkt_len and grp_ptr
+ * list the turn's CANDIDATES per group as qfec_accumulate_ragged's tables do;
+ * pkt_idx[p] is the candidate's position in its group (0 .. K-1 a data packet,
+ * K the FEC packet) and pkt_ok[p] the open call's ok[p] (pkt_ok == NULL: all
+ * verified).  With s = slot[g] (slot == NULL: s = g), K = slot_k[s] (protected
+ * packets, 1..255) and lim = min(1452, acc_stride), the slot's map is the
+ * first K / 8 + 1 bytes at acc_map + s * map_stride, bits as for
+ * qfec_revive_ragged.
+ * Fresh slot: if acc_len[s] == 0 the map counts as all clear whatever it holds
+ * (as row bytes beyond old do for the accumulate), so a slot released by
+ * qfec_revive_accumulated, qfec_revive_tracked or qfec_emit_accumulated needs
+ * no clearing.  Otherwise base = the map's bits 0 .. K; higher bits are ignored.
+ * The group's candidates are taken in CSR order (INVALID over FAILED over
+ * DUPLICATE):
+ *   pkt_idx[p] > K                          QFEC_PKT_INVALID (latched, below)
+ *   pkt_len[p] == 0 or > lim                QFEC_PKT_INVALID (latched)
+ *   pkt_ok given and pkt_ok[p] == 0         QFEC_PKT_FAILED, a result
+ *   its bit set in base, or by an earlier
+ *   candidate of this group in this call    QFEC_PKT_DUPLICATE, a result
+ *   anything else                           QFEC_PKT_ADMITTED, and its bit is set
+ * The first candidate of an index wins: deterministic, and nothing is sorted.
+ * Outputs: verdict[p] for every candidate of a group with k_g <= 255;
+ * grp_ptr_out[0] = 0 and grp_ptr_out[g+1] - grp_ptr_out[g] = the packets
+ * admitted for g; pkt_off_out / pkt_len_out at grp_ptr_out[g] + r the r-th
+ * admitted packet of g in CSR order -- the tables qfec_accumulate_ragged then
+ * folds; entries from grp_ptr_out[n_groups] on are not written.  If g admitted
+ * at least one packet its map's K / 8 + 1 bytes become base | new with zero
+ * bits above K; otherwise no byte of its map is written.  Map bytes beyond
+ * K / 8 + 1 and the maps of slots no group names are never read or written.
+ * counts[0..3] (may be NULL): the verdicts written, per code.
+ * Invalid group: each of its packets is QFEC_PKT_INVALID, none is admitted
+ * and its map is untouched -- k_g > 255 (its verdicts are not written and not
+ * counted: a grp_ptr that is not monotone shows up as that); s >= n_slots
+ * (slot_k, acc_len and the map are then not read); K == 0 or
+ * K / 8 + 1 > map_stride; acc_len[s] > lim.  These and the two invalid-packet
+ * cases are latched on the device and returned by the next qfec_sync as
+ * -QUIC_INVALID_FEC_DATA; every other group's outputs are right.
+ * The caller guarantees, unchecked: the slots named in one call are distinct;
+ * the output tables have room for grp_ptr[n_groups] - grp_ptr[0] entries (no
+ * entry is written past that); each admit is followed on the same stream by a
+ * qfec_accumulate_ragged over its output tables with the same slot, n_slots,
+ * acc_stride and acc_len, before the next admit or close that names those
+ * slots.  With that the accumulate cannot latch for an admitted group, and a
+ * slot with a set bit has acc_len > 0.  A group with K = 255 whose 256 packets
+ * all arrive in one turn needs two calls (k_g <= 255).
+ * Refused on the host (nothing launched, nothing written): acc_stride == 0 or
+ * map_stride == 0 (-QUIC_INVALID_FEC_DATA); QFEC_PTR_HOST, QFEC_PTR_MAPPED or
+ * QFEC_ASYNC; a NULL buffer other than pkt_ok, slot and counts;
+ * n_groups >= 2^32 or n_slots >= 2^32; slot == NULL with n_slots < n_groups
+ * (QFEC_ERR_INTERNAL).  n_groups == 0 succeeds before the buffers are looked at
+ * (counts, if given, receives four zeroes; grp_ptr_out is not written).
+ * QFEC_CACHED and QFEC_SMALL_GROUPS are accepted and change nothing.  Device
+ * pointers only; the call only queues kernels on the context's stream, never
+ * waits and never reads anything back; its intermediate state (per-group and
+ * per-tile counts, scanned offsets) lives in the context-owned scratch of
+ * qfec_revive_batch.
+ *
+ * qfec_revive_tracked is qfec_revive_accumulated with two differences: K and
+ * the map are read by slot, slot_k[s] and acc_map + s * map_stride, and a slot
+ * with acc_len[s] == 0 counts as an all-clear map, so it is
+ * QFEC_GROUP_UNREVIVABLE (a result, not an error; its map is not read) -- the
+ * case "revived but length 0" cannot arise from a stale map.  For every group
+ * whose slot is in range the outputs (status, revived_idx, revived_list,
+ * counts, out_len, copied bytes, releases) are byte for byte what
+ * qfec_revive_accumulated gives when handed group_k[g] = slot_k[slot[g]] and
+ * the by-slot maps gathered by group, zeroed where the slot is fresh.  A slot
+ * out of range is unrevivable and latched like there; its slot_k, map and
+ * length are not read.  Refusals, out == NULL, release_mask and the "never
+ * read / never written" lists are those of qfec_revive_accumulated (slot_k and
+ * acc_map in the place of group_k and received). */
+#define QFEC_PKT_ADMITTED 0u  /* to be folded: its bit was clear and is now set */
+#define QFEC_PKT_FAILED 1u    /* pkt_ok[p] == 0: its protection did not verify */
+#define QFEC_PKT_DUPLICATE 2u /* its bit was already set in the slot's map, or an
+                                 earlier packet of this group in this call set it */
+#define QFEC_PKT_INVALID 3u   /* bad index or length, or its group is invalid */
+int qfec_admit_ragged(qfec_ctx* ctx, const uint64_t* pkt_off, const uint16_t* pkt_len,
+                      const uint8_t* pkt_idx, const uint8_t* pkt_ok, const uint32_t* grp_ptr,
+                      uint64_t n_groups, const uint32_t* slot, uint64_t n_slots,
+                      const uint8_t* slot_k, uint8_t* acc_map, uint64_t map_stride,
+                      const uint16_t* acc_len, uint64_t acc_stride, uint32_t* grp_ptr_out,
+                      uint64_t* pkt_off_out, uint16_t* pkt_len_out, uint8_t* verdict,
+                      uint64_t* counts, uint32_t flags);
+int qfec_revive_tracked(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride, uint16_t* acc_len,
+                        const uint8_t* acc_map, uint64_t map_stride, const uint8_t* slot_k,
+                        const uint32_t* slot, uint64_t n_slots, uint64_t n_groups, uint8_t* out,
+                        const uint64_t* out_off, uint16_t* out_len, uint8_t* status,
+                        uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
+                        uint32_t release_mask, uint32_t flags);
 
 /* ---- single buffer ------------------------------------------------------ */
 /* out[j] ^= in[j] for j < n (QuicFecGroupInterface::XorBuffers). */

@@ -2282,6 +2282,135 @@ int qfec_revive_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stri
   return revive_scratch_release(ctx);
 }
 
+// QuicFecGroup::Update's "already in received_packets_" and the framer's drop
+// of a packet that failed to decrypt, for running rows: decide / scan / scatter
+// on the stream, in the revive calls' scratch.  Every check that needs the
+// tables is the kernels'.
+int qfec_admit_ragged(qfec_ctx* ctx, const uint64_t* pkt_off, const uint16_t* pkt_len,
+                      const uint8_t* pkt_idx, const uint8_t* pkt_ok, const uint32_t* grp_ptr,
+                      uint64_t n_groups, const uint32_t* slot, uint64_t n_slots,
+                      const uint8_t* slot_k, uint8_t* acc_map, uint64_t map_stride,
+                      const uint16_t* acc_len, uint64_t acc_stride, uint32_t* grp_ptr_out,
+                      uint64_t* pkt_off_out, uint16_t* pkt_len_out, uint8_t* verdict,
+                      uint64_t* counts, uint32_t flags) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  ctx->last_ticket = 0;
+  if (ctx->debug_fail)
+    return fail(ctx, QFEC_ERR_INTERNAL, "launch failure injected (qfec_debug_fail_launches)");
+  if (acc_stride == 0)
+    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+                "accumulator stride 0: a row holds the longest packet folded into it");
+  if (map_stride == 0)
+    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+                "receive map stride 0: a group of k packets needs k / 8 + 1 bytes");
+  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "ragged admit: device pointers only, queued on the context's stream "
+                "(QFEC_PTR_HOST, QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)");
+  if (n_groups == 0) {
+    if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, 4 * sizeof(uint64_t), ctx->stream));
+    return QFEC_OK;
+  }
+  if (!pkt_off || !pkt_len || !pkt_idx || !grp_ptr || !slot_k || !acc_map || !acc_len ||
+      !grp_ptr_out || !pkt_off_out || !pkt_len_out || !verdict)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "ragged admit: null buffer (only pkt_ok, slot and counts may be NULL)");
+  if (n_groups >= (1ull << 32) || n_slots >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "ragged admit: 2^32 or more groups or slots (packet and slot indices are 32 "
+                "bits)");
+  if (!slot && n_slots < n_groups)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "ragged admit: slot == NULL admits group g to slot g, and there are fewer slots "
+                "than groups");
+  if ((rc = revive_scratch_acquire(ctx, n_groups))) return rc;
+  qfec::AdmitArgs a{};
+  a.pkt_off = pkt_off;
+  a.pkt_len = pkt_len;
+  a.pkt_idx = pkt_idx;
+  a.pkt_ok = pkt_ok;
+  a.grp_ptr = grp_ptr;
+  a.slot = slot;
+  a.slot_k = slot_k;
+  a.acc_map = acc_map;
+  a.map_stride = map_stride;
+  a.acc_len = acc_len;
+  a.n_groups = n_groups;
+  a.grp_ptr_out = grp_ptr_out;
+  a.pkt_off_out = pkt_off_out;
+  a.pkt_len_out = pkt_len_out;
+  a.verdict = verdict;
+  a.counts = counts;
+  a.err = ctx->d_err;
+  a.n_slots = (uint32_t)n_slots;
+  a.lim = (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
+  qfec::admit_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_admit_ragged(a, ctx->stream));
+  return revive_scratch_release(ctx);
+}
+
+// qfec_revive_accumulated with the group's K and map kept per slot, where
+// qfec_admit_ragged maintains them.
+int qfec_revive_tracked(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride, uint16_t* acc_len,
+                        const uint8_t* acc_map, uint64_t map_stride, const uint8_t* slot_k,
+                        const uint32_t* slot, uint64_t n_slots, uint64_t n_groups, uint8_t* out,
+                        const uint64_t* out_off, uint16_t* out_len, uint8_t* status,
+                        uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
+                        uint32_t release_mask, uint32_t flags) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  ctx->last_ticket = 0;
+  if (ctx->debug_fail)
+    return fail(ctx, QFEC_ERR_INTERNAL, "launch failure injected (qfec_debug_fail_launches)");
+  if (acc_stride == 0)
+    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+                "accumulator stride 0: a row holds the longest packet folded into it");
+  if (map_stride == 0)
+    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+                "receive map stride 0: a group of k packets needs k / 8 + 1 bytes");
+  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
+    return close_check(ctx, "revive tracked", n_slots, n_groups, slot, flags);
+  if (release_mask > 7u)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "revive tracked: release_mask 0x%x has bits above the three group statuses",
+                release_mask);
+  if (n_groups == 0) {
+    if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(uint64_t), ctx->stream));
+    return QFEC_OK;
+  }
+  if (!acc || !acc_len || !slot_k || !acc_map || (out && !out_off) || !out_len || !status)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "revive tracked: null buffer (only slot, out, out_off without out, "
+                "revived_idx, revived_list and counts may be NULL)");
+  if ((rc = close_check(ctx, "revive tracked", n_slots, n_groups, slot, flags))) return rc;
+  if ((rc = revive_scratch_acquire(ctx, n_groups))) return rc;
+  qfec::TrackedCloseArgs a{};
+  a.acc = acc;
+  a.acc_stride = acc_stride;
+  a.acc_len = acc_len;
+  a.slot = slot;
+  a.slot_k = slot_k;
+  a.acc_map = acc_map;
+  a.map_stride = map_stride;
+  a.n_groups = n_groups;
+  a.out = out;
+  a.out_off = out_off;
+  a.out_len = out_len;
+  a.status = status;
+  a.revived_idx = revived_idx;
+  a.revived_list = revived_list;
+  a.counts = counts;
+  a.err = ctx->d_err;
+  a.n_slots = (uint32_t)n_slots;
+  a.lim = (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
+  a.release = release_mask;
+  a.ncu = ctx->ncu;
+  qfec::revive_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_tracked_revive(a, ctx->stream));
+  return revive_scratch_release(ctx);
+}
+
 int qfec_xor_into(qfec_ctx* ctx, const uint8_t* in, uint64_t n, uint8_t* out, uint32_t flags) {
   int rc = bind(ctx);
   if (rc) return rc;

@@ -10,11 +10,13 @@ namespace qfec {
 
 // Bits latched into the context's device error word by kernels.
 enum : uint32_t {
-  kErrMissingIndex = 1u,  // missing_idx >= k; accumulate: slot >= n_slots
+  kErrMissingIndex = 1u,  // missing_idx >= k; accumulate: slot >= n_slots; admit: slot >=
+                          // n_slots or pkt_idx > K; tracked revive: slot >= n_slots
   kErrPacketLength = 2u,  // ragged packet length 0 or > kMaxPacketSize, or > parity_len
-                          // (accumulate: > min(kMaxPacketSize, acc_stride))
-  kErrGroupSize = 4u,     // ragged group with 0 or > 255 packets (accumulate: > 255)
-  kErrParityLength = 8u,  // ragged parity_len 0 or > kMaxPacketSize; accumulate:
+                          // (accumulate, admit: > min(kMaxPacketSize, acc_stride))
+  kErrGroupSize = 4u,     // ragged group with 0 or > 255 packets (accumulate, admit: > 255);
+                          // admit, tracked revive: slot_k 0 or its map beyond map_stride
+  kErrParityLength = 8u,  // ragged parity_len 0 or > kMaxPacketSize; accumulate, admit:
                           // acc_len > min(kMaxPacketSize, acc_stride)
 };
 
@@ -259,6 +261,94 @@ hipError_t launch_close_emit(const CloseArgs& a, hipStream_t s);
 // Four launches on s (classify, scan, emit, the gather over the work list;
 // three when out == nullptr), ordered by the stream alone.  n_groups > 0.
 hipError_t launch_close_revive(const CloseArgs& a, hipStream_t s);
+
+// qfec_revive_tracked: CloseArgs's revive with K and the map read by SLOT
+// (slot_k[s], acc_map + s * map_stride) and a slot of length 0 counting as an
+// all-clear map.  A struct of its own (CloseArgs keeps its kernarg layout); the
+// fields CloseArgs has keep their names, so the gather over the work list is
+// CloseArgs's own kernel, handed a CloseArgs filled from this.
+struct TrackedCloseArgs {
+  const uint8_t* acc;
+  uint64_t acc_stride;
+  uint16_t* acc_len;     // read; zeroed for released slots
+  const uint32_t* slot;  // nullable
+  const uint8_t* slot_k;
+  const uint8_t* acc_map;
+  uint64_t map_stride;
+  uint64_t n_groups;  // < 2^32
+  uint8_t* out;       // nullable
+  const uint64_t* out_off;
+  uint16_t* out_len;
+  uint8_t* status;
+  uint8_t* revived_idx;    // nullable
+  uint64_t* revived_list;  // nullable
+  uint64_t* counts;        // nullable: [complete, revived, unrevivable]
+  // scratch, as ReviveArgs (revive_scratch_bytes(n_groups))
+  uint32_t* tile_cnt;
+  uint64_t* tile_off;
+  uint64_t* totals;
+  uint64_t* work;
+  uint32_t* err;
+  uint32_t n_slots;
+  uint32_t lim;
+  uint32_t release;
+  uint32_t ncu;
+};
+inline void revive_scratch_layout(TrackedCloseArgs& a, void* block) {
+  uint8_t* p = static_cast<uint8_t*>(block);
+  a.totals = reinterpret_cast<uint64_t*>(p);
+  a.work = reinterpret_cast<uint64_t*>(p + 32);
+  a.tile_off = a.work + a.n_groups + kReviveListPad;
+  a.tile_cnt = reinterpret_cast<uint32_t*>(a.tile_off + revive_tiles(a.n_groups));
+}
+// Launches as launch_close_revive.  n_groups > 0.
+hipError_t launch_tracked_revive(const TrackedCloseArgs& a, hipStream_t s);
+
+// qfec_admit_ragged: filter a turn's candidates against the per-slot running
+// maps and the open call's ok flags, and write the CSR tables the accumulate
+// folds (layout and rule as include/qfec.h).  Verdict codes: QFEC_PKT_*.
+// Scratch, inside a revive_scratch_bytes(n_groups) block: per group its
+// admitted count (in the work list's place, which also holds the four verdict
+// counts of every tile of kReviveTile groups behind them), per tile the
+// admitted packets of the tiles before it.
+struct AdmitArgs {
+  const uint64_t* pkt_off;
+  const uint16_t* pkt_len;
+  const uint8_t* pkt_idx;
+  const uint8_t* pkt_ok;  // nullable: all verified
+  const uint32_t* grp_ptr;
+  const uint32_t* slot;  // nullable
+  const uint8_t* slot_k;
+  uint8_t* acc_map;
+  uint64_t map_stride;
+  const uint16_t* acc_len;
+  uint64_t n_groups;  // < 2^32
+  uint32_t* grp_ptr_out;
+  uint64_t* pkt_off_out;
+  uint16_t* pkt_len_out;
+  uint8_t* verdict;
+  uint64_t* counts;  // nullable: [admitted, failed, duplicate, invalid]
+  uint32_t* grp_cnt;   // scratch: n_groups
+  uint32_t* tile_v;    // scratch: 4 per tile
+  uint64_t* tile_off;  // scratch: 1 per tile
+  uint32_t* err;
+  uint32_t n_slots;
+  uint32_t lim;  // min(kMaxPacket, acc_stride): longest packet / row
+};
+inline void admit_scratch_layout(AdmitArgs& a, void* block) {
+  uint8_t* p = static_cast<uint8_t*>(block);
+  a.grp_cnt = reinterpret_cast<uint32_t*>(p + 32);
+  a.tile_v = a.grp_cnt + a.n_groups;
+  a.tile_off = reinterpret_cast<uint64_t*>(p + 32) + a.n_groups + kReviveListPad;
+}
+// the work list's (n_groups + kReviveListPad) * 8 bytes hold both tables: a
+// full tile's 16 bytes fit the 4 bytes per group its counts leave, the last
+// tile's fit the pad
+static_assert(kReviveTile * 4 >= 16 && kReviveListPad * 8 >= 16,
+              "n_groups * 4 + tiles * 16 <= (n_groups + kReviveListPad) * 8");
+// Three launches on s (decide, scan, scatter), ordered by the stream alone.
+// n_groups > 0.
+hipError_t launch_admit_ragged(const AdmitArgs& a, hipStream_t s);
 
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch

@@ -47,6 +47,11 @@
 //    aligned (close_gather_kernel) -- over every group for the emit, over the
 //    revive's work list (classify / scan / emit with k per group from group_k)
 //    for the receiver's close.
+//  * The receive maps on the device (qfec_admit_ragged / qfec_revive_tracked):
+//    one running map per slot; decide / scan / scatter filter a turn's
+//    candidates against it and the open call's ok flags into the tables the
+//    accumulate folds (admit_*_kernel), and the receiver's close reads K and
+//    the map by slot (the classify kernels instantiated for TrackedCloseArgs).
 #include "qfec_internal.h"
 
 #include <algorithm>
@@ -819,6 +824,60 @@ __device__ __forceinline__ uint64_t revive_emit_group(const CloseArgs& a, uint64
   return (uint64_t)len << kCloseLenShift;
 }
 
+// Where a valid group's map starts: by group for the three argument structs
+// above, by slot for TrackedCloseArgs.
+template <typename Args>
+__device__ __forceinline__ const uint8_t* revive_map(const Args& a, uint64_t g) {
+  return a.received + g * a.map_stride;
+}
+
+// TrackedCloseArgs (qfec_revive_tracked): CloseArgs's rules with K = slot_k[s]
+// and the map of slot s.  A slot out of range (kErrMissingIndex; slot_k, map
+// and length not read) or a bad K (kErrGroupSize; map and length not read) is
+// unrevivable, and so is a FRESH slot, acc_len[s] == 0: its map counts as all
+// clear whatever it holds, which is no error and is not read either.
+__device__ __forceinline__ uint32_t close_slot(const TrackedCloseArgs& a, uint64_t g) {
+  return a.slot ? a.slot[g] : (uint32_t)g;
+}
+__device__ __forceinline__ bool close_k_ok(const TrackedCloseArgs& a, uint32_t k) {
+  return k >= 1u && (uint64_t)(k / 8u + 1u) <= a.map_stride;
+}
+__device__ __forceinline__ bool revive_group_k(const TrackedCloseArgs& a, uint64_t g,
+                                               uint32_t& k) {
+  const uint32_t s = close_slot(a, g);
+  k = 0;
+  if (s >= a.n_slots) return false;
+  k = a.slot_k[s];
+  return close_k_ok(a, k) && a.acc_len[s] != 0;
+}
+__device__ __forceinline__ void revive_bad_group(const TrackedCloseArgs& a, uint64_t g) {
+  const uint32_t s = close_slot(a, g);
+  if (s >= a.n_slots) atomicOr(a.err, kErrMissingIndex);
+  else if (!close_k_ok(a, a.slot_k[s])) atomicOr(a.err, kErrGroupSize);
+}
+__device__ __forceinline__ const uint8_t* revive_map(const TrackedCloseArgs& a, uint64_t g) {
+  return a.acc_map + (uint64_t)close_slot(a, g) * a.map_stride;
+}
+// As CloseArgs's: a fresh slot arrives here unrevivable, its length 0 already.
+__device__ __forceinline__ uint64_t revive_emit_group(const TrackedCloseArgs& a, uint64_t g,
+                                                      uint32_t st) {
+  if (st > kGroupUnrevivable) return 0ull;
+  const uint32_t s = close_slot(a, g);
+  uint32_t len = 0;
+  if (s < a.n_slots && close_k_ok(a, a.slot_k[s])) {
+    bool ok = true;
+    if (st == kGroupRevived) {
+      const uint32_t l = a.acc_len[s];
+      ok = l >= 1u && l <= a.lim;
+      if (ok) len = l;
+      else atomicOr(a.err, kErrParityLength);
+    }
+    if (ok && ((a.release >> st) & 1u) != 0u) a.acc_len[s] = 0;
+  }
+  a.out_len[g] = (uint16_t)len;
+  return (uint64_t)len << kCloseLenShift;
+}
+
 template <bool EMIT, typename Args>
 __global__ __launch_bounds__(kReviveTile) void revive_classify_kernel(Args a) {
   __shared__ uint32_t s_w[kReviveTile / 64];
@@ -830,7 +889,7 @@ __global__ __launch_bounds__(kReviveTile) void revive_classify_kernel(Args a) {
     if (g < a.n_groups) {
       uint32_t k;
       if (revive_group_k(a, g, k)) {
-        st = revive_classify(a.received + g * a.map_stride, k, m);
+        st = revive_classify(revive_map(a, g), k, m);
       } else {
         st = kGroupUnrevivable;
         if constexpr (!EMIT) revive_bad_group(a, g);
@@ -915,6 +974,249 @@ __global__ __launch_bounds__(kRvScanBlock) void revive_scan_kernel(Args a) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------
+// Admission to running rows (qfec_admit_ragged): the group's received-packets
+// set on the device, consulted before the fold.
+// ---------------------------------------------------------------------------
+// Three kernels on the stream, the pattern of the revive above (tile counts,
+// a one-workgroup scan, ranks from the scanned counts); none reads a payload
+// byte:
+//   decide  : one lane per group walks its candidates in CSR order with the
+//             slot's map (bits 0..K, all clear for a fresh slot) in eight LDS
+//             words of its own: verdict[p], the group's admitted count, the
+//             tile's four verdict counts, and the map back if anything was
+//             admitted.  The first candidate of an index wins because the walk
+//             is serial: deterministic, no sort, no atomics on the map;
+//   scan    : one workgroup, an exclusive scan over the tiles' admitted
+//             counts, the four totals and grp_ptr_out[n_groups];
+//   scatter : a scan of the tile's 256 group counts gives grp_ptr_out[g]; the
+//             lane walks its group's verdicts again and copies the admitted
+//             packets' table entries in order.
+// All map arithmetic is on 32-bit words (the gfx950 64-bit shift hazard).
+constexpr uint32_t kPktAdmitted = 0, kPktFailed = 1, kPktDuplicate = 2, kPktInvalid = 3;
+constexpr uint32_t kAdmitMapWords = 8;  // bits 0..K, K <= 255
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+__global__ __launch_bounds__(kReviveTile) void admit_decide_kernel(AdmitArgs a) {
+  __shared__ uint32_t s_map[kAdmitMapWords][kReviveTile];  // word-major: no bank conflicts
+  __shared__ uint32_t s_w[kReviveTile / 64][4];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const uint64_t g = tile * kReviveTile + tid;
+    uint32_t c_adm = 0, c_fail = 0, c_dup = 0, c_inv = 0;
+    if (g < a.n_groups) {
+      const uint32_t p0 = a.grp_ptr[g];
+      const uint32_t kg = a.grp_ptr[g + 1] - p0;  // a non-monotone grp_ptr shows up as kg > 255
+      uint32_t bad = 0;
+      if (kg > 255u) {
+        bad = kErrGroupSize;  // its verdicts are not written
+      } else {
+        const uint32_t s = a.slot ? a.slot[g] : (uint32_t)g;
+        uint32_t K = 0, old = 0;
+        if (s >= a.n_slots) {
+          bad = kErrMissingIndex;
+        } else {
+          K = a.slot_k[s];
+          old = a.acc_len[s];
+          if (K == 0u || (uint64_t)(K / 8u + 1u) > a.map_stride) bad |= kErrGroupSize;
+          if (old > a.lim) bad |= kErrParityLength;
+        }
+        if (bad != 0u) {
+          for (uint32_t j = 0; j < kg; ++j) a.verdict[p0 + j] = (uint8_t)kPktInvalid;
+          c_inv = kg;
+        } else {
+          uint8_t* mp = a.acc_map + (uint64_t)s * a.map_stride;
+          const uint32_t nb = K / 8u + 1u, nbit = K + 1u;
+          // base: the map's bits 0..K, or nothing for a fresh slot
+#pragma unroll
+          for (uint32_t w = 0; w < kAdmitMapWords; ++w) {
+            uint32_t x = 0;
+            if (old != 0u && 4u * w < nb) {
+#pragma unroll
+              for (uint32_t b = 0; b < 4u; ++b)
+                if (4u * w + b < nb) x |= (uint32_t)mp[4u * w + b] << (8u * b);
+              if (nbit < 32u * w + 32u) x &= (1u << (nbit - 32u * w)) - 1u;  // shift 1..31
+            }
+            s_map[w][tid] = x;
+          }
+          uint32_t pkt_bad = 0;
+          for (uint32_t j = 0; j < kg; ++j) {
+            const uint32_t p = p0 + j;
+            const uint32_t idx = a.pkt_idx[p], len = a.pkt_len[p];
+            const uint32_t okp = a.pkt_ok ? (uint32_t)a.pkt_ok[p] : 1u;
+            uint32_t e = 0;
+            if (idx > K) e |= kErrMissingIndex;
+            if (len == 0u || len > a.lim) e |= kErrPacketLength;
+            uint32_t v;
+            if (e != 0u) {
+              v = kPktInvalid;
+              pkt_bad |= e;
+            } else if (okp == 0u) {
+              v = kPktFailed;
+            } else {
+              const uint32_t w = idx >> 5, bit = 1u << (idx & 31u);
+              const uint32_t cur = s_map[w][tid];
+              v = (cur & bit) != 0u ? kPktDuplicate : kPktAdmitted;
+              s_map[w][tid] = cur | bit;
+            }
+            a.verdict[p] = (uint8_t)v;
+            c_adm += v == kPktAdmitted ? 1u : 0u;
+            c_fail += v == kPktFailed ? 1u : 0u;
+            c_dup += v == kPktDuplicate ? 1u : 0u;
+            c_inv += v == kPktInvalid ? 1u : 0u;
+          }
+          if (c_adm != 0u)  // base | new, zero above bit K
+            for (uint32_t b = 0; b < nb; ++b)
+              mp[b] = (uint8_t)(s_map[b >> 2][tid] >> (8u * (b & 3u)));
+          if (pkt_bad != 0u) atomicOr(a.err, pkt_bad);
+        }
+      }
+      if (bad != 0u) atomicOr(a.err, bad);
+      a.grp_cnt[g] = c_adm;
+    }
+    const uint32_t w_adm = wave_sum(c_adm), w_fail = wave_sum(c_fail), w_dup = wave_sum(c_dup),
+                   w_inv = wave_sum(c_inv);
+    if (lane == 0u) {
+      s_w[wave][kPktAdmitted] = w_adm;
+      s_w[wave][kPktFailed] = w_fail;
+      s_w[wave][kPktDuplicate] = w_dup;
+      s_w[wave][kPktInvalid] = w_inv;
+    }
+    __syncthreads();
+    if (tid < 4u) a.tile_v[tile * 4u + tid] = s_w[0][tid] + s_w[1][tid] + s_w[2][tid] + s_w[3][tid];
+    __syncthreads();  // s_w is reused by the next tile
+  }
+}
+
+// One workgroup: tile_off[i] = packets admitted in the tiles before i, then
+// the totals.
+__global__ __launch_bounds__(kRvScanBlock) void admit_scan_kernel(AdmitArgs a) {
+  __shared__ uint32_t s_adm[kRvScanBlock / 64];
+  __shared__ unsigned long long s_tot[3];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
+  if (tid < 3u) s_tot[tid] = 0ull;
+  uint64_t base = 0, fail = 0, dup = 0, inv = 0;
+  for (uint64_t t0 = 0; t0 < ntile; t0 += kRvScanBlock) {
+    const uint64_t i = t0 + tid;
+    uint32_t adm = 0;
+    if (i < ntile) {
+      adm = a.tile_v[i * 4u + kPktAdmitted];
+      fail += a.tile_v[i * 4u + kPktFailed];
+      dup += a.tile_v[i * 4u + kPktDuplicate];
+      inv += a.tile_v[i * 4u + kPktInvalid];
+    }
+    uint32_t x = adm;  // inclusive scan within the wave
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63u) s_adm[wave] = x;
+    __syncthreads();
+    uint32_t before = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kRvScanBlock / 64; ++w) {
+      if (w < wave) before += s_adm[w];
+      tot += s_adm[w];
+    }
+    if (i < ntile) a.tile_off[i] = base + before + (x - adm);
+    base += tot;
+    __syncthreads();
+  }
+  if (fail != 0ull) atomicAdd(&s_tot[0], (unsigned long long)fail);
+  if (dup != 0ull) atomicAdd(&s_tot[1], (unsigned long long)dup);
+  if (inv != 0ull) atomicAdd(&s_tot[2], (unsigned long long)inv);
+  __syncthreads();
+  if (tid == 0u) {
+    a.grp_ptr_out[a.n_groups] = (uint32_t)base;
+    if (a.counts) {
+      a.counts[kPktAdmitted] = base;
+      a.counts[kPktFailed] = s_tot[0];
+      a.counts[kPktDuplicate] = s_tot[1];
+      a.counts[kPktInvalid] = s_tot[2];
+    }
+  }
+}
+
+// grp_ptr_out[g] and the admitted packets' table entries, stable.  `room`:
+// the candidates the tables list, grp_ptr[n_groups] - grp_ptr[0] -- with a
+// grp_ptr that is not monotone (latched by the decide pass) the valid groups
+// can claim more, and no entry is written past it.
+__global__ __launch_bounds__(kReviveTile) void admit_scatter_kernel(AdmitArgs a) {
+  __shared__ uint32_t s_w[kReviveTile / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
+  const uint32_t room = a.grp_ptr[a.n_groups] - a.grp_ptr[0];
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const uint64_t g = tile * kReviveTile + tid;
+    const uint32_t cnt = g < a.n_groups ? a.grp_cnt[g] : 0u;
+    uint32_t x = cnt;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63u) s_w[wave] = x;
+    __syncthreads();
+    uint32_t pos = (uint32_t)a.tile_off[tile] + (x - cnt);
+    for (uint32_t w = 0; w < wave; ++w) pos += s_w[w];
+    uint32_t p0 = 0, kg = 0;
+    if (g < a.n_groups) {
+      a.grp_ptr_out[g] = pos;
+      p0 = a.grp_ptr[g];
+      kg = a.grp_ptr[g + 1] - p0;
+    }
+    // Every group of the tile valid in size: their candidates are one
+    // contiguous run of the tables, each with a verdict, and an admitted
+    // packet's place is the tile's plus the admitted packets before it in the
+    // run -- one lane per PACKET, loads and stores coalesced (a lane per group
+    // touches a cache line per lane and store: 6x the time on 2^20 groups).
+    if (__syncthreads_and(kg <= 255u ? 1 : 0)) {  // (also orders s_w's reads and writes)
+      const uint64_t gend = min((tile + 1) * (uint64_t)kReviveTile, a.n_groups);
+      const uint32_t first = a.grp_ptr[tile * kReviveTile], end = a.grp_ptr[gend];
+      uint32_t base = (uint32_t)a.tile_off[tile];
+      for (uint64_t q = first; q < end; q += kReviveTile) {  // (uniform; 64-bit: no wrap)
+        const uint64_t p = q + tid;
+        const bool adm = p < end && a.verdict[p] == (uint8_t)kPktAdmitted;
+        const uint64_t b = __ballot(adm);
+        if (lane == 0u) s_w[wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t r = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32),
+                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        for (uint32_t w = 0; w < wave; ++w) r += s_w[w];
+        if (adm && r < room) {
+          a.pkt_off_out[r] = a.pkt_off[p];
+          a.pkt_len_out[r] = a.pkt_len[p];
+        }
+        base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        __syncthreads();  // s_w is reused by the next step and the next tile
+      }
+    } else {
+      // a group of more than 255 candidates in the tile (its verdicts are not
+      // written, and grp_ptr need not be monotone around it): group by group
+      if (cnt != 0u) {
+        for (uint32_t j = 0, r = 0; j < kg && r < cnt; ++j) {
+          if (a.verdict[p0 + j] != (uint8_t)kPktAdmitted) continue;
+          if (pos + r < room) {
+            a.pkt_off_out[pos + r] = a.pkt_off[p0 + j];
+            a.pkt_len_out[pos + r] = a.pkt_len[p0 + j];
+          }
+          ++r;
+        }
+      }
+      __syncthreads();  // s_w is reused by the next tile
+    }
+  }
+}
+static_assert(kReviveTile == 256, "four waves' counts are summed by hand above");
 
 // The recover body over the work list, L >= 16: lanes, windows and loads as
 // fixed_xor_kernel; workgroup step i takes entries [i * gpb, (i + 1) * gpb).
@@ -3354,6 +3656,48 @@ hipError_t launch_close_revive(const CloseArgs& a, hipStream_t s) {
   // the count stays on the device: the grid is sized by the worst case
   hipLaunchKernelGGL(close_gather_kernel<true>, dim3(close_gather_grid(a)), dim3(kBlock), 0, s, a,
                      a.work, a.totals);
+  return hipGetLastError();
+}
+
+hipError_t launch_tracked_revive(const TrackedCloseArgs& a, hipStream_t s) {
+  if (a.n_groups == 0) return hipSuccess;
+  const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
+  hipLaunchKernelGGL((revive_classify_kernel<false, TrackedCloseArgs>), dim3(cgrid),
+                     dim3(kReviveTile), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(revive_scan_kernel<TrackedCloseArgs>, dim3(1), dim3(kRvScanBlock), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL((revive_classify_kernel<true, TrackedCloseArgs>), dim3(cgrid),
+                     dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (!a.out) return hipSuccess;  // the revived packets are the rows
+  // the gather over the work list is qfec_revive_accumulated's: an entry
+  // carries its group and length, the rest is the slot table and the rows
+  CloseArgs c{};
+  c.acc = a.acc;
+  c.acc_stride = a.acc_stride;
+  c.slot = a.slot;
+  c.n_groups = a.n_groups;
+  c.out = a.out;
+  c.out_off = a.out_off;
+  c.n_slots = a.n_slots;
+  c.lim = a.lim;
+  c.ncu = a.ncu;
+  hipLaunchKernelGGL(close_gather_kernel<true>, dim3(close_gather_grid(c)), dim3(kBlock), 0, s, c,
+                     a.work, a.totals);
+  return hipGetLastError();
+}
+
+hipError_t launch_admit_ragged(const AdmitArgs& a, hipStream_t s) {
+  if (a.n_groups == 0) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
+  hipLaunchKernelGGL(admit_decide_kernel, dim3(grid), dim3(kReviveTile), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(admit_scan_kernel, dim3(1), dim3(kRvScanBlock), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(admit_scatter_kernel, dim3(grid), dim3(kReviveTile), 0, s, a);
   return hipGetLastError();
 }
 

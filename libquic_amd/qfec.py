@@ -33,6 +33,10 @@ QFEC_PENDING = 1
 GROUP_COMPLETE = 0
 GROUP_REVIVED = 1
 GROUP_UNREVIVABLE = 2
+QFEC_PKT_ADMITTED = 0
+QFEC_PKT_FAILED = 1
+QFEC_PKT_DUPLICATE = 2
+QFEC_PKT_INVALID = 3
 MAX_PACKET_SIZE = 1452
 DEFAULT_MAX_PACKET_SIZE = 1350
 MAX_GROUP_PACKETS = 255
@@ -88,6 +92,12 @@ SIGNATURES = [
       C.c_uint32]),
     ("qfec_revive_accumulated", C.c_int,
      [_vp, _u8p, C.c_uint64, _vp, _vp, C.c_uint64, _u8p, _u8p, C.c_uint64, C.c_uint64, _u8p, _vp,
+      _vp, _u8p, _u8p, _vp, _vp, C.c_uint32, C.c_uint32]),
+    ("qfec_admit_ragged", C.c_int,
+     [_vp, _vp, _vp, _u8p, _u8p, _vp, C.c_uint64, _vp, C.c_uint64, _u8p, _u8p, C.c_uint64, _vp,
+      C.c_uint64, _vp, _vp, _vp, _u8p, _vp, C.c_uint32]),
+    ("qfec_revive_tracked", C.c_int,
+     [_vp, _u8p, C.c_uint64, _vp, _u8p, C.c_uint64, _u8p, _vp, C.c_uint64, C.c_uint64, _u8p, _vp,
       _vp, _u8p, _u8p, _vp, _vp, C.c_uint32, C.c_uint32]),
     ("qfec_xor_into", C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint32]),
     ("qfec_wire_write_private_header", C.c_size_t, [_vp, _u8p, C.c_size_t]),
@@ -513,6 +523,44 @@ class Context:
                                               _ptr(out_len), _ptr(status), _ptr(revived_idx),
                                               _ptr(revived_list), _ptr(counts), release_mask,
                                               flags)
+        return self._check(rc)
+
+    def admit_ragged(self, pkt_off, pkt_len, pkt_idx, pkt_ok, grp_ptr, n_groups, slot_k, acc_map,
+                     map_stride, acc_len, acc_stride, grp_ptr_out, pkt_off_out, pkt_len_out,
+                     verdict, *, slot=None, n_slots=None, counts=None, flags=0):
+        """qfec_admit_ragged: filter a turn's candidates (CSR tables; pkt_idx
+        uint8 the position in the group, pkt_ok uint8 the open call's ok or
+        None) against the running map of slot s = slot[g] (uint32[n]; None:
+        s = g) of K = slot_k[s] protected packets, acc_map + s * map_stride.
+        verdict[p] (uint8) receives a QFEC_PKT_* code, grp_ptr_out (uint32[n +
+        1]), pkt_off_out and pkt_len_out the tables of the admitted packets
+        for accumulate_ragged, counts (uint64[4], optional) the verdicts per
+        code; the maps gain the admitted bits.  n_slots=None: n_groups.
+        Device pointers only; queued on the context's stream (sync() before
+        reading the results)."""
+        ns = n_groups if n_slots is None else n_slots
+        rc = self.lib.qfec_admit_ragged(self.ctx, _ptr(pkt_off), _ptr(pkt_len), _ptr(pkt_idx),
+                                        _ptr(pkt_ok), _ptr(grp_ptr), n_groups, _ptr(slot), ns,
+                                        _ptr(slot_k), _ptr(acc_map), map_stride, _ptr(acc_len),
+                                        acc_stride, _ptr(grp_ptr_out), _ptr(pkt_off_out),
+                                        _ptr(pkt_len_out), _ptr(verdict), _ptr(counts), flags)
+        return self._check(rc)
+
+    def revive_tracked(self, acc, acc_stride, acc_len, acc_map, map_stride, slot_k, n_groups, out,
+                       out_off, out_len, *, status, slot=None, n_slots=None, revived_idx=None,
+                       revived_list=None, counts=None, release_mask=0, flags=0):
+        """qfec_revive_tracked: revive_accumulated with K and the map read by
+        slot (slot_k uint8[n_slots], acc_map + s * map_stride, as admit_ragged
+        keeps them); a slot of length 0 counts as an all-clear map and is
+        unrevivable.  Outputs, release_mask and out None as revive_accumulated.
+        n_slots=None: n_groups.  Device pointers only; queued on the
+        context's stream (sync() before reading the results)."""
+        ns = n_groups if n_slots is None else n_slots
+        rc = self.lib.qfec_revive_tracked(self.ctx, _ptr(acc), acc_stride, _ptr(acc_len),
+                                          _ptr(acc_map), map_stride, _ptr(slot_k), _ptr(slot), ns,
+                                          n_groups, _ptr(out), _ptr(out_off), _ptr(out_len),
+                                          _ptr(status), _ptr(revived_idx), _ptr(revived_list),
+                                          _ptr(counts), release_mask, flags)
         return self._check(rc)
 
     def xor_into(self, src, n, dst, *, host=False, mapped=False):
