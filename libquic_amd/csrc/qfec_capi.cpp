@@ -1456,6 +1456,67 @@ int revive_scratch_release(qfec_ctx* ctx) {
   return QFEC_OK;
 }
 
+// ---- the host checks of the queued, device-pointer-only calls --------------
+// Each call makes the ones it has, in its order, under its name (`what`); the
+// order is pinned by tests/test_hip_queued_refusals.py.
+
+// How qfec_accumulate_ragged and the calls after it begin: no ticket, and the
+// injected launch failure.  (qfec_revive_batch and qfec_revive_ragged, older
+// than both, only bind; that difference is kept.)
+int begin_queued(qfec_ctx* ctx, const char* what) {
+  const int rc = bind(ctx);
+  if (rc) return rc;
+  ctx->last_ticket = 0;
+  if (ctx->debug_fail)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: launch failure injected (qfec_debug_fail_launches)", what);
+  return QFEC_OK;
+}
+
+int check_acc_stride(qfec_ctx* ctx, const char* what, uint64_t acc_stride) {
+  if (acc_stride != 0) return QFEC_OK;
+  return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+              "%s: accumulator stride 0: a row holds the longest packet folded into it", what);
+}
+
+int check_map_stride(qfec_ctx* ctx, const char* what, uint64_t map_stride) {
+  if (map_stride != 0) return QFEC_OK;
+  return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
+              "%s: receive map stride 0: a group of k packets needs k / 8 + 1 bytes", what);
+}
+
+int check_device_only(qfec_ctx* ctx, const char* what, uint32_t flags) {
+  if ((flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC)) == 0) return QFEC_OK;
+  return fail(ctx, QFEC_ERR_INTERNAL,
+              "%s: device pointers only, queued on the context's stream (QFEC_PTR_HOST, "
+              "QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)", what);
+}
+
+// Groups and slots are indexed with 32 bits; without a slot table group g has slot g.
+int check_index_range(qfec_ctx* ctx, const char* what, uint64_t n_groups, uint64_t n_slots,
+                      const uint32_t* slot) {
+  if (n_groups >= (1ull << 32) || n_slots >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: 2^32 or more groups or slots (packet, group and slot indices are 32 bits)",
+                what);
+  if (!slot && n_slots < n_groups)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: slot == NULL gives group g slot g, and there are fewer slots than groups",
+                what);
+  return QFEC_OK;
+}
+
+// What an empty batch still owes the caller: its counts, all zero.
+int zero_counts(qfec_ctx* ctx, uint64_t* counts, size_t words) {
+  if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, words * sizeof(uint64_t), ctx->stream));
+  return QFEC_OK;
+}
+
+// The longest packet a running row of acc_stride bytes holds (the structs' lim).
+uint32_t row_limit(uint64_t acc_stride) {
+  return (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
+}
+
 }  // namespace
 
 // Revive from per-group receive maps: the receiver half of QuicFecGroup
@@ -1471,25 +1532,23 @@ int qfec_revive_batch_strided(qfec_ctx* ctx, uint8_t* rows, const uint8_t* parit
                               uint8_t* out, uint64_t out_stride, uint8_t* status,
                               uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
                               uint32_t flags) {
-  int rc = bind(ctx);
+  const char* const what = "revive";
+  int rc = bind(ctx);  // (not begin_queued: see there)
   if (rc) return rc;
   if ((rc = check_fixed(ctx, k, L, row_stride, group_stride, parity_stride, out ? out_stride : L)))
     return rc;
   if (map_stride < (uint64_t)k / 8u + 1u)
     return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
-                "receive map stride %llu smaller than the %u bytes of %u + 1 bits",
+                "%s: receive map stride %llu smaller than the %u bytes of %u + 1 bits", what,
                 (unsigned long long)map_stride, k / 8u + 1u, k);
-  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
+  if ((rc = check_device_only(ctx, what, flags))) return rc;
+  if (n_groups == 0) return zero_counts(ctx, counts, 3);
+  if (!rows || !parity || !received || !status)
     return fail(ctx, QFEC_ERR_INTERNAL,
-                "revive from receive maps: device pointers only, queued on the context's stream "
-                "(QFEC_PTR_HOST, QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)");
-  if (n_groups == 0) {
-    if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(uint64_t), ctx->stream));
-    return QFEC_OK;
-  }
-  if (!rows || !parity || !received || !status) return fail(ctx, QFEC_ERR_INTERNAL, "null buffer");
+                "%s: null buffer (only out, revived_idx, revived_list and counts may be NULL)",
+                what);
   if (n_groups >= (1ull << 56))
-    return fail(ctx, QFEC_ERR_INTERNAL, "more than 2^56 groups");
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: 2^56 or more groups", what);
   if ((rc = revive_scratch_acquire(ctx, n_groups))) return rc;
   qfec::ReviveArgs a{};
   a.rows = rows;
@@ -2063,27 +2122,19 @@ int qfec_revive_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt_
                        uint8_t* out, const uint64_t* out_off, uint8_t* status,
                        uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
                        uint32_t flags) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  if (map_stride == 0)
-    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
-                "receive map stride 0: a group of k packets needs k / 8 + 1 bytes");
-  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "ragged revive from receive maps: device pointers only, queued on the context's "
-                "stream (QFEC_PTR_HOST, QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)");
-  if (n_groups == 0) {
-    if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(uint64_t), ctx->stream));
-    return QFEC_OK;
-  }
+  const char* const what = "ragged revive";
+  int rc = bind(ctx);  // (not begin_queued: see there)
+  if (rc || (rc = check_map_stride(ctx, what, map_stride)) ||
+      (rc = check_device_only(ctx, what, flags)))
+    return rc;
+  if (n_groups == 0) return zero_counts(ctx, counts, 3);
   if (!bytes || !pkt_off || !pkt_len || !grp_ptr || !parity || !parity_off || !parity_len ||
       !received || !out || !out_off || !status)
     return fail(ctx, QFEC_ERR_INTERNAL,
-                "ragged revive: null buffer (only revived_idx, revived_list and counts may be "
-                "NULL)");
+                "%s: null buffer (only revived_idx, revived_list and counts may be NULL)", what);
   if (n_groups >= (1ull << 32))
     return fail(ctx, QFEC_ERR_INTERNAL,
-                "ragged revive: 2^32 or more groups (packet indices are 32 bits)");
+                "%s: 2^32 or more groups (packet indices are 32 bits)", what);
   if ((rc = revive_scratch_acquire(ctx, n_groups))) return rc;
   qfec::ReviveRaggedArgs a{};
   a.bytes = bytes;
@@ -2117,29 +2168,15 @@ int qfec_accumulate_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* 
                            const uint16_t* pkt_len, const uint32_t* grp_ptr, uint64_t n_groups,
                            uint8_t* acc, uint64_t acc_stride, uint16_t* acc_len,
                            const uint32_t* slot, uint64_t n_slots, uint32_t flags) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  ctx->last_ticket = 0;
-  if (ctx->debug_fail)
-    return fail(ctx, QFEC_ERR_INTERNAL, "launch failure injected (qfec_debug_fail_launches)");
-  if (acc_stride == 0)
-    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
-                "accumulator stride 0: a row holds the longest packet folded into it");
-  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "ragged accumulate: device pointers only, queued on the context's stream "
-                "(QFEC_PTR_HOST, QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)");
+  const char* const what = "ragged accumulate";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_acc_stride(ctx, what, acc_stride)) ||
+      (rc = check_device_only(ctx, what, flags)))
+    return rc;
   if (n_groups == 0) return QFEC_OK;
   if (!bytes || !pkt_off || !pkt_len || !grp_ptr || !acc || !acc_len)
-    return fail(ctx, QFEC_ERR_INTERNAL, "ragged accumulate: null buffer (only slot may be NULL)");
-  if (n_groups >= (1ull << 32) || n_slots >= (1ull << 32))
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "ragged accumulate: 2^32 or more groups or slots (packet and slot indices are "
-                "32 bits)");
-  if (!slot && n_slots < n_groups)
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "ragged accumulate: slot == NULL folds group g into slot g, and there are fewer "
-                "slots than groups");
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: null buffer (only slot may be NULL)", what);
+  if ((rc = check_index_range(ctx, what, n_groups, n_slots, slot))) return rc;
   qfec::AccumulateRaggedArgs a{};
   a.bytes = bytes;
   a.pkt_off = pkt_off;
@@ -2151,33 +2188,11 @@ int qfec_accumulate_ragged(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* 
   a.slot = slot;
   a.n_groups = n_groups;
   a.n_slots = (uint32_t)n_slots;
-  a.lim = (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
+  a.lim = row_limit(acc_stride);
   a.err = ctx->d_err;
   QFEC_HIP(ctx, qfec::launch_accumulate_ragged(a, ctx->stream));
   return QFEC_OK;
 }
-
-namespace {
-
-// The host checks the two closing calls share (what: the call's name in the
-// messages); QFEC_OK: launch.
-int close_check(qfec_ctx* ctx, const char* what, uint64_t n_slots, uint64_t n_groups,
-                const uint32_t* slot, uint32_t flags) {
-  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "%s: device pointers only, queued on the context's stream (QFEC_PTR_HOST, "
-                "QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)", what);
-  if (n_groups >= (1ull << 32) || n_slots >= (1ull << 32))
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "%s: 2^32 or more groups or slots (group and slot indices are 32 bits)", what);
-  if (!slot && n_slots < n_groups)
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "%s: slot == NULL closes slot g for group g, and there are fewer slots than "
-                "groups", what);
-  return QFEC_OK;
-}
-
-}  // namespace
 
 // QuicFecGroup::PayloadParity for running rows: one gather launch, which also
 // writes the lengths and releases the slots.
@@ -2185,21 +2200,15 @@ int qfec_emit_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride
                           uint16_t* acc_len, const uint32_t* slot, uint64_t n_slots,
                           uint64_t n_groups, uint8_t* out, const uint64_t* out_off,
                           uint16_t* out_len, int release, uint32_t flags) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  ctx->last_ticket = 0;
-  if (ctx->debug_fail)
-    return fail(ctx, QFEC_ERR_INTERNAL, "launch failure injected (qfec_debug_fail_launches)");
-  if (acc_stride == 0)
-    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
-                "accumulator stride 0: a row holds the longest packet folded into it");
-  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
-    return close_check(ctx, "emit accumulated", n_slots, n_groups, slot, flags);
+  const char* const what = "emit accumulated";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_acc_stride(ctx, what, acc_stride)) ||
+      (rc = check_device_only(ctx, what, flags)))
+    return rc;
   if (n_groups == 0) return QFEC_OK;
   if (!acc || !acc_len || !out || !out_off || !out_len)
-    return fail(ctx, QFEC_ERR_INTERNAL, "emit accumulated: null buffer (only slot may be NULL)");
-  if ((rc = close_check(ctx, "emit accumulated", n_slots, n_groups, slot, flags)))
-    return rc;
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: null buffer (only slot may be NULL)", what);
+  if ((rc = check_index_range(ctx, what, n_groups, n_slots, slot))) return rc;
   qfec::CloseArgs a{};
   a.acc = acc;
   a.acc_stride = acc_stride;
@@ -2211,52 +2220,41 @@ int qfec_emit_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride
   a.out_len = out_len;
   a.err = ctx->d_err;
   a.n_slots = (uint32_t)n_slots;
-  a.lim = (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
+  a.lim = row_limit(acc_stride);
   a.release = release != 0 ? 1u : 0u;
   a.ncu = ctx->ncu;
   QFEC_HIP(ctx, qfec::launch_close_emit(a, ctx->stream));
   return QFEC_OK;
 }
 
-// The receiver's close (NumMissingPackets / CanRevive / Revive, then the
-// group is deleted) for running rows: classify / scan / emit as the other
-// revives, sharing their scratch, then the gather over the work list.
-int qfec_revive_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride,
-                            uint16_t* acc_len, const uint32_t* slot, uint64_t n_slots,
-                            const uint8_t* group_k, const uint8_t* received, uint64_t map_stride,
-                            uint64_t n_groups, uint8_t* out, const uint64_t* out_off,
-                            uint16_t* out_len, uint8_t* status, uint8_t* revived_idx,
-                            uint64_t* revived_list, uint64_t* counts, uint32_t release_mask,
-                            uint32_t flags) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  ctx->last_ticket = 0;
-  if (ctx->debug_fail)
-    return fail(ctx, QFEC_ERR_INTERNAL, "launch failure injected (qfec_debug_fail_launches)");
-  if (acc_stride == 0)
-    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
-                "accumulator stride 0: a row holds the longest packet folded into it");
-  if (map_stride == 0)
-    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
-                "receive map stride 0: a group of k packets needs k / 8 + 1 bytes");
-  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
-    return close_check(ctx, "revive accumulated", n_slots, n_groups, slot, flags);
+namespace {
+
+// qfec_revive_accumulated and qfec_revive_tracked: one call but for where K and
+// the maps live -- per group (group_k, received) or, tracked, per slot (the
+// call's slot_k and acc_map, which take the same two members).
+int revive_closing(qfec_ctx* ctx, const char* what, bool tracked, const uint8_t* acc,
+                   uint64_t acc_stride, uint16_t* acc_len, const uint32_t* slot, uint64_t n_slots,
+                   const uint8_t* group_k, const uint8_t* received, uint64_t map_stride,
+                   uint64_t n_groups, uint8_t* out, const uint64_t* out_off, uint16_t* out_len,
+                   uint8_t* status, uint8_t* revived_idx, uint64_t* revived_list,
+                   uint64_t* counts, uint32_t release_mask, uint32_t flags) {
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_acc_stride(ctx, what, acc_stride)) ||
+      (rc = check_map_stride(ctx, what, map_stride)) ||
+      (rc = check_device_only(ctx, what, flags)))
+    return rc;
   if (release_mask > 7u)
     return fail(ctx, QFEC_ERR_INTERNAL,
-                "revive accumulated: release_mask 0x%x has bits above the three group statuses",
+                "%s: release_mask 0x%x has bits above the three group statuses", what,
                 release_mask);
-  if (n_groups == 0) {
-    if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(uint64_t), ctx->stream));
-    return QFEC_OK;
-  }
+  if (n_groups == 0) return zero_counts(ctx, counts, 3);
   if (!acc || !acc_len || !group_k || !received || (out && !out_off) || !out_len || !status)
     return fail(ctx, QFEC_ERR_INTERNAL,
-                "revive accumulated: null buffer (only slot, out, out_off without out, "
-                "revived_idx, revived_list and counts may be NULL)");
-  if ((rc = close_check(ctx, "revive accumulated", n_slots, n_groups, slot, flags)))
-    return rc;
+                "%s: null buffer (only slot, out, out_off without out, revived_idx, "
+                "revived_list and counts may be NULL)", what);
+  if ((rc = check_index_range(ctx, what, n_groups, n_slots, slot))) return rc;
   if ((rc = revive_scratch_acquire(ctx, n_groups))) return rc;
-  qfec::CloseArgs a{};
+  qfec::TrackedCloseArgs a{};  // (a CloseArgs under either name)
   a.acc = acc;
   a.acc_stride = acc_stride;
   a.acc_len = acc_len;
@@ -2274,12 +2272,32 @@ int qfec_revive_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stri
   a.counts = counts;
   a.err = ctx->d_err;
   a.n_slots = (uint32_t)n_slots;
-  a.lim = (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
+  a.lim = row_limit(acc_stride);
   a.release = release_mask;
   a.ncu = ctx->ncu;
   qfec::revive_scratch_layout(a, ctx->d_revive);
-  QFEC_HIP(ctx, qfec::launch_close_revive(a, ctx->stream));
+  if (tracked)
+    QFEC_HIP(ctx, qfec::launch_tracked_revive(a, ctx->stream));
+  else
+    QFEC_HIP(ctx, qfec::launch_close_revive(a, ctx->stream));
   return revive_scratch_release(ctx);
+}
+
+}  // namespace
+
+// The receiver's close (NumMissingPackets / CanRevive / Revive, then the
+// group is deleted) for running rows: classify / scan / emit as the other
+// revives, sharing their scratch, then the gather over the work list.
+int qfec_revive_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride,
+                            uint16_t* acc_len, const uint32_t* slot, uint64_t n_slots,
+                            const uint8_t* group_k, const uint8_t* received, uint64_t map_stride,
+                            uint64_t n_groups, uint8_t* out, const uint64_t* out_off,
+                            uint16_t* out_len, uint8_t* status, uint8_t* revived_idx,
+                            uint64_t* revived_list, uint64_t* counts, uint32_t release_mask,
+                            uint32_t flags) {
+  return revive_closing(ctx, "revive accumulated", false, acc, acc_stride, acc_len, slot, n_slots,
+                        group_k, received, map_stride, n_groups, out, out_off, out_len, status,
+                        revived_idx, revived_list, counts, release_mask, flags);
 }
 
 // QuicFecGroup::Update's "already in received_packets_" and the framer's drop
@@ -2293,37 +2311,18 @@ int qfec_admit_ragged(qfec_ctx* ctx, const uint64_t* pkt_off, const uint16_t* pk
                       const uint16_t* acc_len, uint64_t acc_stride, uint32_t* grp_ptr_out,
                       uint64_t* pkt_off_out, uint16_t* pkt_len_out, uint8_t* verdict,
                       uint64_t* counts, uint32_t flags) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  ctx->last_ticket = 0;
-  if (ctx->debug_fail)
-    return fail(ctx, QFEC_ERR_INTERNAL, "launch failure injected (qfec_debug_fail_launches)");
-  if (acc_stride == 0)
-    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
-                "accumulator stride 0: a row holds the longest packet folded into it");
-  if (map_stride == 0)
-    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
-                "receive map stride 0: a group of k packets needs k / 8 + 1 bytes");
-  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "ragged admit: device pointers only, queued on the context's stream "
-                "(QFEC_PTR_HOST, QFEC_PTR_MAPPED and QFEC_ASYNC are not supported)");
-  if (n_groups == 0) {
-    if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, 4 * sizeof(uint64_t), ctx->stream));
-    return QFEC_OK;
-  }
+  const char* const what = "ragged admit";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_acc_stride(ctx, what, acc_stride)) ||
+      (rc = check_map_stride(ctx, what, map_stride)) ||
+      (rc = check_device_only(ctx, what, flags)))
+    return rc;
+  if (n_groups == 0) return zero_counts(ctx, counts, 4);
   if (!pkt_off || !pkt_len || !pkt_idx || !grp_ptr || !slot_k || !acc_map || !acc_len ||
       !grp_ptr_out || !pkt_off_out || !pkt_len_out || !verdict)
     return fail(ctx, QFEC_ERR_INTERNAL,
-                "ragged admit: null buffer (only pkt_ok, slot and counts may be NULL)");
-  if (n_groups >= (1ull << 32) || n_slots >= (1ull << 32))
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "ragged admit: 2^32 or more groups or slots (packet and slot indices are 32 "
-                "bits)");
-  if (!slot && n_slots < n_groups)
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "ragged admit: slot == NULL admits group g to slot g, and there are fewer slots "
-                "than groups");
+                "%s: null buffer (only pkt_ok, slot and counts may be NULL)", what);
+  if ((rc = check_index_range(ctx, what, n_groups, n_slots, slot))) return rc;
   if ((rc = revive_scratch_acquire(ctx, n_groups))) return rc;
   qfec::AdmitArgs a{};
   a.pkt_off = pkt_off;
@@ -2344,7 +2343,7 @@ int qfec_admit_ragged(qfec_ctx* ctx, const uint64_t* pkt_off, const uint16_t* pk
   a.counts = counts;
   a.err = ctx->d_err;
   a.n_slots = (uint32_t)n_slots;
-  a.lim = (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
+  a.lim = row_limit(acc_stride);
   qfec::admit_scratch_layout(a, ctx->d_revive);
   QFEC_HIP(ctx, qfec::launch_admit_ragged(a, ctx->stream));
   return revive_scratch_release(ctx);
@@ -2358,57 +2357,9 @@ int qfec_revive_tracked(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride, 
                         const uint64_t* out_off, uint16_t* out_len, uint8_t* status,
                         uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
                         uint32_t release_mask, uint32_t flags) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  ctx->last_ticket = 0;
-  if (ctx->debug_fail)
-    return fail(ctx, QFEC_ERR_INTERNAL, "launch failure injected (qfec_debug_fail_launches)");
-  if (acc_stride == 0)
-    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
-                "accumulator stride 0: a row holds the longest packet folded into it");
-  if (map_stride == 0)
-    return fail(ctx, QFEC_ERR_INVALID_FEC_DATA,
-                "receive map stride 0: a group of k packets needs k / 8 + 1 bytes");
-  if (flags & (QFEC_PTR_HOST | QFEC_PTR_MAPPED | QFEC_ASYNC))
-    return close_check(ctx, "revive tracked", n_slots, n_groups, slot, flags);
-  if (release_mask > 7u)
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "revive tracked: release_mask 0x%x has bits above the three group statuses",
-                release_mask);
-  if (n_groups == 0) {
-    if (counts) QFEC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(uint64_t), ctx->stream));
-    return QFEC_OK;
-  }
-  if (!acc || !acc_len || !slot_k || !acc_map || (out && !out_off) || !out_len || !status)
-    return fail(ctx, QFEC_ERR_INTERNAL,
-                "revive tracked: null buffer (only slot, out, out_off without out, "
-                "revived_idx, revived_list and counts may be NULL)");
-  if ((rc = close_check(ctx, "revive tracked", n_slots, n_groups, slot, flags))) return rc;
-  if ((rc = revive_scratch_acquire(ctx, n_groups))) return rc;
-  qfec::TrackedCloseArgs a{};
-  a.acc = acc;
-  a.acc_stride = acc_stride;
-  a.acc_len = acc_len;
-  a.slot = slot;
-  a.slot_k = slot_k;
-  a.acc_map = acc_map;
-  a.map_stride = map_stride;
-  a.n_groups = n_groups;
-  a.out = out;
-  a.out_off = out_off;
-  a.out_len = out_len;
-  a.status = status;
-  a.revived_idx = revived_idx;
-  a.revived_list = revived_list;
-  a.counts = counts;
-  a.err = ctx->d_err;
-  a.n_slots = (uint32_t)n_slots;
-  a.lim = (uint32_t)std::min<uint64_t>(QFEC_MAX_PACKET_SIZE, acc_stride);
-  a.release = release_mask;
-  a.ncu = ctx->ncu;
-  qfec::revive_scratch_layout(a, ctx->d_revive);
-  QFEC_HIP(ctx, qfec::launch_tracked_revive(a, ctx->stream));
-  return revive_scratch_release(ctx);
+  return revive_closing(ctx, "revive tracked", true, acc, acc_stride, acc_len, slot, n_slots,
+                        slot_k, acc_map, map_stride, n_groups, out, out_off, out_len, status,
+                        revived_idx, revived_list, counts, release_mask, flags);
 }
 
 int qfec_xor_into(qfec_ctx* ctx, const uint8_t* in, uint64_t n, uint8_t* out, uint32_t flags) {

@@ -105,11 +105,13 @@ struct ReviveArgs {
 inline uint64_t revive_tiles(uint64_t n_groups) {
   return (n_groups + kReviveTile - 1) / kReviveTile;
 }
-// Bytes of scratch for n_groups, and the four pointers into a block of them.
+// Bytes of scratch for n_groups, and the four pointers into a block of them
+// (Args: any of the revive argument structs; they name the four alike).
 inline uint64_t revive_scratch_bytes(uint64_t n_groups) {
   return 32 + (n_groups + kReviveListPad) * 8 + revive_tiles(n_groups) * 12;
 }
-inline void revive_scratch_layout(ReviveArgs& a, void* block) {
+template <typename Args>
+inline void revive_scratch_layout(Args& a, void* block) {
   uint8_t* p = static_cast<uint8_t*>(block);
   a.totals = reinterpret_cast<uint64_t*>(p);
   a.work = reinterpret_cast<uint64_t*>(p + 32);
@@ -175,13 +177,6 @@ struct ReviveRaggedArgs {
   uint32_t* err;
   uint32_t ncu;
 };
-inline void revive_scratch_layout(ReviveRaggedArgs& a, void* block) {
-  uint8_t* p = static_cast<uint8_t*>(block);
-  a.totals = reinterpret_cast<uint64_t*>(p);
-  a.work = reinterpret_cast<uint64_t*>(p + 32);
-  a.tile_off = a.work + a.n_groups + kReviveListPad;
-  a.tile_cnt = reinterpret_cast<uint32_t*>(a.tile_off + revive_tiles(a.n_groups));
-}
 // Four launches on s (classify, scan, emit, the ragged block body over the
 // work list), ordered by the stream alone.  n_groups > 0.
 hipError_t launch_revive_ragged(const ReviveRaggedArgs& a, hipStream_t s);
@@ -227,6 +222,9 @@ struct CloseArgs {
   uint64_t acc_stride;
   uint16_t* acc_len;     // read; zeroed for released slots
   const uint32_t* slot;  // nullable
+  // K and the receive maps, map_stride apart.  CloseArgs: per GROUP
+  // (group_k[g], received + g * map_stride).  TrackedCloseArgs: per SLOT
+  // (the call's slot_k[s] and acc_map + s * map_stride)
   const uint8_t* group_k;
   const uint8_t* received;
   uint64_t map_stride;
@@ -249,13 +247,6 @@ struct CloseArgs {
   uint32_t release;
   uint32_t ncu;
 };
-inline void revive_scratch_layout(CloseArgs& a, void* block) {
-  uint8_t* p = static_cast<uint8_t*>(block);
-  a.totals = reinterpret_cast<uint64_t*>(p);
-  a.work = reinterpret_cast<uint64_t*>(p + 32);
-  a.tile_off = a.work + a.n_groups + kReviveListPad;
-  a.tile_cnt = reinterpret_cast<uint32_t*>(a.tile_off + revive_tiles(a.n_groups));
-}
 // One launch on s: the gather over every group.  n_groups > 0.
 hipError_t launch_close_emit(const CloseArgs& a, hipStream_t s);
 // Four launches on s (classify, scan, emit, the gather over the work list;
@@ -263,44 +254,11 @@ hipError_t launch_close_emit(const CloseArgs& a, hipStream_t s);
 hipError_t launch_close_revive(const CloseArgs& a, hipStream_t s);
 
 // qfec_revive_tracked: CloseArgs's revive with K and the map read by SLOT
-// (slot_k[s], acc_map + s * map_stride) and a slot of length 0 counting as an
-// all-clear map.  A struct of its own (CloseArgs keeps its kernarg layout); the
-// fields CloseArgs has keep their names, so the gather over the work list is
-// CloseArgs's own kernel, handed a CloseArgs filled from this.
-struct TrackedCloseArgs {
-  const uint8_t* acc;
-  uint64_t acc_stride;
-  uint16_t* acc_len;     // read; zeroed for released slots
-  const uint32_t* slot;  // nullable
-  const uint8_t* slot_k;
-  const uint8_t* acc_map;
-  uint64_t map_stride;
-  uint64_t n_groups;  // < 2^32
-  uint8_t* out;       // nullable
-  const uint64_t* out_off;
-  uint16_t* out_len;
-  uint8_t* status;
-  uint8_t* revived_idx;    // nullable
-  uint64_t* revived_list;  // nullable
-  uint64_t* counts;        // nullable: [complete, revived, unrevivable]
-  // scratch, as ReviveArgs (revive_scratch_bytes(n_groups))
-  uint32_t* tile_cnt;
-  uint64_t* tile_off;
-  uint64_t* totals;
-  uint64_t* work;
-  uint32_t* err;
-  uint32_t n_slots;
-  uint32_t lim;
-  uint32_t release;
-  uint32_t ncu;
-};
-inline void revive_scratch_layout(TrackedCloseArgs& a, void* block) {
-  uint8_t* p = static_cast<uint8_t*>(block);
-  a.totals = reinterpret_cast<uint64_t*>(p);
-  a.work = reinterpret_cast<uint64_t*>(p + 32);
-  a.tile_off = a.work + a.n_groups + kReviveListPad;
-  a.tile_cnt = reinterpret_cast<uint32_t*>(a.tile_off + revive_tiles(a.n_groups));
-}
+// (group_k[s], received + s * map_stride) and a slot of length 0 counting as
+// an all-clear map.  The same layout under a type of its own, which selects
+// the by-slot classify hooks; the gather over the work list is CloseArgs's own
+// kernel and takes these arguments as the CloseArgs they are.
+struct TrackedCloseArgs : CloseArgs {};
 // Launches as launch_close_revive.  n_groups > 0.
 hipError_t launch_tracked_revive(const TrackedCloseArgs& a, hipStream_t s);
 

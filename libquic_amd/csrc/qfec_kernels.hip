@@ -799,31 +799,6 @@ __device__ __forceinline__ void revive_bad_group(const CloseArgs& a, uint64_t g)
   if (close_slot(a, g) >= a.n_slots) atomicOr(a.err, kErrMissingIndex);
   if (!close_k_ok(a, a.group_k[g])) atomicOr(a.err, kErrGroupSize);
 }
-// out_len and the release, one lane per group: a revived group's length is
-// read here, ONCE, and travels in its work-list entry (the gather never reads
-// acc_len), so the zero stored below cannot reach the copy.  A revived group
-// whose length is 0 or above the limit latches kErrParityLength: out_len 0,
-// entry length 0 (nothing copied), no release.  Invalid groups: out_len 0, no
-// release.
-__device__ __forceinline__ uint64_t revive_emit_group(const CloseArgs& a, uint64_t g,
-                                                      uint32_t st) {
-  if (st > kGroupUnrevivable) return 0ull;
-  const uint32_t s = close_slot(a, g);
-  uint32_t len = 0;
-  if (s < a.n_slots && close_k_ok(a, a.group_k[g])) {
-    bool ok = true;
-    if (st == kGroupRevived) {
-      const uint32_t l = a.acc_len[s];
-      ok = l >= 1u && l <= a.lim;
-      if (ok) len = l;
-      else atomicOr(a.err, kErrParityLength);
-    }
-    if (ok && ((a.release >> st) & 1u) != 0u) a.acc_len[s] = 0;
-  }
-  a.out_len[g] = (uint16_t)len;
-  return (uint64_t)len << kCloseLenShift;
-}
-
 // Where a valid group's map starts: by group for the three argument structs
 // above, by slot for TrackedCloseArgs.
 template <typename Args>
@@ -831,40 +806,51 @@ __device__ __forceinline__ const uint8_t* revive_map(const Args& a, uint64_t g) 
   return a.received + g * a.map_stride;
 }
 
-// TrackedCloseArgs (qfec_revive_tracked): CloseArgs's rules with K = slot_k[s]
-// and the map of slot s.  A slot out of range (kErrMissingIndex; slot_k, map
-// and length not read) or a bad K (kErrGroupSize; map and length not read) is
-// unrevivable, and so is a FRESH slot, acc_len[s] == 0: its map counts as all
-// clear whatever it holds, which is no error and is not read either.
-__device__ __forceinline__ uint32_t close_slot(const TrackedCloseArgs& a, uint64_t g) {
-  return a.slot ? a.slot[g] : (uint32_t)g;
-}
-__device__ __forceinline__ bool close_k_ok(const TrackedCloseArgs& a, uint32_t k) {
-  return k >= 1u && (uint64_t)(k / 8u + 1u) <= a.map_stride;
-}
+// TrackedCloseArgs (qfec_revive_tracked): CloseArgs's rules with K =
+// group_k[s] and the map of slot s.  A slot out of range (kErrMissingIndex; K,
+// map and length not read) or a bad K (kErrGroupSize; map and length not read)
+// is unrevivable, and so is a FRESH slot, acc_len[s] == 0: its map counts as
+// all clear whatever it holds, which is no error and is not read either.
 __device__ __forceinline__ bool revive_group_k(const TrackedCloseArgs& a, uint64_t g,
                                                uint32_t& k) {
   const uint32_t s = close_slot(a, g);
   k = 0;
   if (s >= a.n_slots) return false;
-  k = a.slot_k[s];
+  k = a.group_k[s];
   return close_k_ok(a, k) && a.acc_len[s] != 0;
 }
 __device__ __forceinline__ void revive_bad_group(const TrackedCloseArgs& a, uint64_t g) {
   const uint32_t s = close_slot(a, g);
   if (s >= a.n_slots) atomicOr(a.err, kErrMissingIndex);
-  else if (!close_k_ok(a, a.slot_k[s])) atomicOr(a.err, kErrGroupSize);
+  else if (!close_k_ok(a, a.group_k[s])) atomicOr(a.err, kErrGroupSize);
 }
 __device__ __forceinline__ const uint8_t* revive_map(const TrackedCloseArgs& a, uint64_t g) {
-  return a.acc_map + (uint64_t)close_slot(a, g) * a.map_stride;
+  return a.received + (uint64_t)close_slot(a, g) * a.map_stride;
 }
-// As CloseArgs's: a fresh slot arrives here unrevivable, its length 0 already.
-__device__ __forceinline__ uint64_t revive_emit_group(const TrackedCloseArgs& a, uint64_t g,
-                                                      uint32_t st) {
+
+// The K of group g, which sits in slot s: the one thing the EMIT pass below
+// reads differently for the two closes.
+__device__ __forceinline__ uint32_t close_group_k(const CloseArgs& a, uint64_t g, uint32_t) {
+  return a.group_k[g];
+}
+__device__ __forceinline__ uint32_t close_group_k(const TrackedCloseArgs& a, uint64_t,
+                                                  uint32_t s) {
+  return a.group_k[s];
+}
+// The EMIT pass's look for CloseArgs and TrackedCloseArgs (the two revives
+// further up have overloads of their own): out_len and the release, one lane
+// per group.  A revived group's length is read here, ONCE, and travels in its
+// work-list entry (the gather never reads acc_len), so the zero stored below
+// cannot reach the copy.  A revived group whose length is 0 or above the limit
+// latches kErrParityLength: out_len 0, entry length 0 (nothing copied), no
+// release.  Invalid groups: out_len 0, no release.  A fresh slot of
+// TrackedCloseArgs arrives here unrevivable, its length 0 already.
+template <typename Args>
+__device__ __forceinline__ uint64_t revive_emit_group(const Args& a, uint64_t g, uint32_t st) {
   if (st > kGroupUnrevivable) return 0ull;
   const uint32_t s = close_slot(a, g);
   uint32_t len = 0;
-  if (s < a.n_slots && close_k_ok(a, a.slot_k[s])) {
+  if (s < a.n_slots && close_k_ok(a, close_group_k(a, g, s))) {
     bool ok = true;
     if (st == kGroupRevived) {
       const uint32_t l = a.acc_len[s];
@@ -3557,21 +3543,29 @@ hipError_t launch_revive_k(const ReviveArgs& a, uint32_t C, uint32_t gpb, uint32
   return hipGetLastError();
 }
 
+// The first three launches of every revive (classify, scan, emit), for any of
+// the revive argument structs.  classify and emit: grid-stride over the tiles
+// of kReviveTile groups.
+template <typename Args>
+hipError_t launch_revive_passes(const Args& a, hipStream_t s) {
+  const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
+  hipLaunchKernelGGL((revive_classify_kernel<false, Args>), dim3(cgrid), dim3(kReviveTile), 0, s,
+                     a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(revive_scan_kernel<Args>, dim3(1), dim3(kRvScanBlock), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL((revive_classify_kernel<true, Args>), dim3(cgrid), dim3(kReviveTile), 0, s,
+                     a);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_revive(const ReviveArgs& a, bool nontemporal, hipStream_t s) {
   if (a.n_groups == 0) return hipSuccess;
-  // classify and emit: grid-stride over the tiles of kReviveTile groups
-  const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
-  hipLaunchKernelGGL((revive_classify_kernel<false, ReviveArgs>), dim3(cgrid), dim3(kReviveTile), 0,
-                     s, a);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_revive_passes(a, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(revive_scan_kernel<ReviveArgs>, dim3(1), dim3(kRvScanBlock), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL((revive_classify_kernel<true, ReviveArgs>), dim3(cgrid), dim3(kReviveTile), 0,
-                     s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
   // revive: the count stays on the device, so the grid is sized by the device
   // (eight workgroups per CU: every wave slot at up to 64 VGPRs) and by the
   // worst case, whichever is smaller; workgroups loop over the list
@@ -3596,16 +3590,8 @@ constexpr int kRaggedBlockWaves = 4, kRaggedBlockGroups = 8;  // ragged_block_ke
 
 hipError_t launch_revive_ragged(const ReviveRaggedArgs& a, hipStream_t s) {
   if (a.n_groups == 0) return hipSuccess;
-  const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
-  hipLaunchKernelGGL((revive_classify_kernel<false, ReviveRaggedArgs>), dim3(cgrid),
-                     dim3(kReviveTile), 0, s, a);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_revive_passes(a, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(revive_scan_kernel<ReviveRaggedArgs>, dim3(1), dim3(kRvScanBlock), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL((revive_classify_kernel<true, ReviveRaggedArgs>), dim3(cgrid),
-                     dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
   // the count stays on the device: as many blocks as the device holds at once
   // (asked of the runtime: with the VGPRs of this build six per CU, and a grid
   // of eight per CU left a quarter of the blocks to run after the others, at a
@@ -3640,53 +3626,29 @@ hipError_t launch_close_emit(const CloseArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_close_revive(const CloseArgs& a, hipStream_t s) {
+// Both closing revives: the three passes for Args, then the gather over the
+// work list.  The gather is one kernel for both: an entry carries its group and
+// length, and what it reads besides (acc, acc_stride, slot, out, out_off) is
+// CloseArgs's part of either struct.
+template <typename Args>
+static hipError_t launch_close_revive_as(const Args& a, hipStream_t s) {
   if (a.n_groups == 0) return hipSuccess;
-  const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
-  hipLaunchKernelGGL((revive_classify_kernel<false, CloseArgs>), dim3(cgrid), dim3(kReviveTile), 0,
-                     s, a);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_revive_passes(a, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(revive_scan_kernel<CloseArgs>, dim3(1), dim3(kRvScanBlock), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL((revive_classify_kernel<true, CloseArgs>), dim3(cgrid), dim3(kReviveTile), 0,
-                     s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
   if (!a.out) return hipSuccess;  // the revived packets are the rows
   // the count stays on the device: the grid is sized by the worst case
-  hipLaunchKernelGGL(close_gather_kernel<true>, dim3(close_gather_grid(a)), dim3(kBlock), 0, s, a,
+  const CloseArgs& c = a;
+  hipLaunchKernelGGL(close_gather_kernel<true>, dim3(close_gather_grid(c)), dim3(kBlock), 0, s, c,
                      a.work, a.totals);
   return hipGetLastError();
 }
 
+hipError_t launch_close_revive(const CloseArgs& a, hipStream_t s) {
+  return launch_close_revive_as(a, s);
+}
+
 hipError_t launch_tracked_revive(const TrackedCloseArgs& a, hipStream_t s) {
-  if (a.n_groups == 0) return hipSuccess;
-  const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
-  hipLaunchKernelGGL((revive_classify_kernel<false, TrackedCloseArgs>), dim3(cgrid),
-                     dim3(kReviveTile), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(revive_scan_kernel<TrackedCloseArgs>, dim3(1), dim3(kRvScanBlock), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL((revive_classify_kernel<true, TrackedCloseArgs>), dim3(cgrid),
-                     dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  if (!a.out) return hipSuccess;  // the revived packets are the rows
-  // the gather over the work list is qfec_revive_accumulated's: an entry
-  // carries its group and length, the rest is the slot table and the rows
-  CloseArgs c{};
-  c.acc = a.acc;
-  c.acc_stride = a.acc_stride;
-  c.slot = a.slot;
-  c.n_groups = a.n_groups;
-  c.out = a.out;
-  c.out_off = a.out_off;
-  c.n_slots = a.n_slots;
-  c.lim = a.lim;
-  c.ncu = a.ncu;
-  hipLaunchKernelGGL(close_gather_kernel<true>, dim3(close_gather_grid(c)), dim3(kBlock), 0, s, c,
-                     a.work, a.totals);
-  return hipGetLastError();
+  return launch_close_revive_as(a, s);
 }
 
 hipError_t launch_admit_ragged(const AdmitArgs& a, hipStream_t s) {
