@@ -33,8 +33,8 @@
 //    the ragged block body over the list (revive_ragged_kernel).
 //  * Ragged CSR batches: eight groups per 4-wave block in one flat window
 //    space (ragged_block_kernel; the one-group body below is its exact
-//    fallback; the round-1/2 forms, one and two groups per wave, live in
-//    tools/tune/ragged_legacy.inc for the A/B record), lanes own 16-byte
+//    fallback; two groups per wave, ragged_multi_kernel, for large batches of
+//    small groups), lanes own 16-byte
 //    windows of the packets; a window shorter than 16 bytes is loaded as the
 //    16 bytes that end at the packet's last byte and shifted down (zero
 //    fill), so again no load leaves the packet.
@@ -92,25 +92,6 @@ __device__ __forceinline__ void st16t(uint8_t* p, u32x4 v) {
   }
 }
 
-// A 16-B store with an explicit cache policy (round 6 store-policy probe,
-// tools/tune only): 0 nt (the product's st16t<true>), 1 sc1, 2 sc0 sc1,
-// 3 nt sc1, 4 nt sc0 sc1 -- vector stores; sc1 drops the line from the XCD's
-// L2 (write-through), nt keeps it (MI355X_MICROARCH.md, store flavours).
-template <int POL>
-__device__ __forceinline__ void st16pol(uint8_t* p, u32x4 v) {
-  if constexpr (POL == 0) {
-    __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p));
-  } else if constexpr (POL == 1) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-  } else if constexpr (POL == 2) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-  } else if constexpr (POL == 3) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
-  } else {
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(p), "v"(v) : "memory");
-  }
-}
-
 // Wave max of 11-bit values by ballots, MSB first (no LDS round trips).
 __device__ __forceinline__ uint32_t wave_max11(uint32_t v) {
   uint32_t mx = 0;
@@ -123,14 +104,6 @@ __device__ __forceinline__ uint32_t wave_max11(uint32_t v) {
 }
 
 __device__ __forceinline__ bool wave_any(bool p) { return __ballot(p) != 0ull; }
-
-// XCD-aware workgroup order (MI355X_MICROARCH.md, workgroup dispatch: blocks
-// b, b + 8, b + 16, ... share an XCD and its L2): maps those blocks onto one
-// contiguous share of the grid, bijectively for any n (q = n / 8, r = n % 8).
-__device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t n) {
-  const uint32_t q = n >> 3, r = n & 7u, x = b & 7u;
-  return (x < r ? x * (q + 1u) : r * (q + 1u) + (x - r) * q) + (b >> 3);
-}
 
 // N rows r .. r+N-1 of a group, all N loads in flight before the first XOR
 // (recover: row m is the parity row `par`).  The runtime-k bodies use it for
@@ -209,14 +182,22 @@ __device__ __forceinline__ void xor_rows_rt(u32x4& acc, const uint8_t* src, uint
 // group's output row is its own row missing[g] (which held the redundancy);
 // a barrier between the loads and the stores keeps a wave from overwriting
 // the bytes the overlapping last window of a neighbouring wave still reads.
-template <int KC, bool RECOVER, bool NT, bool SM, bool XCD = false, bool INPL = false>
+//
+// Variant measured and removed (the kernel with it as the template switch XCD,
+// and the block mapping itself, are in git history at ace3ed3): XCD-aware
+// workgroup order -- the blocks b, b + 8, ... that share an XCD and its L2
+// take one contiguous share of the groups.  Fixed encode 0.99x, recover 1.00x
+// (profiles/round1/tune_xcd_t2.txt); it does not change a buffer pair's
+// placement mode either, +-1-5% (profiles/round1/place_order_p{1,2}.txt;
+// DESIGN.md §4).  The only reuse between workgroups is one boundary line each.
+template <int KC, bool RECOVER, bool NT, bool SM, bool INPL = false>
 __global__ __launch_bounds__(kBlock) void fixed_xor_kernel(FixedArgs a, uint32_t C,
                                                            uint32_t gpb) {
   static_assert(!(INPL && RECOVER), "in place: the encode form over the k rows");
   const uint32_t tid = threadIdx.x;
   const uint32_t gl = tid / C;  // group within the workgroup
   const uint32_t t = tid - gl * C;
-  const uint64_t gb = (uint64_t)(XCD ? xcd_block(blockIdx.x, gridDim.x) : blockIdx.x) * gpb;
+  const uint64_t gb = (uint64_t)blockIdx.x * gpb;
   const uint64_t g = gb + gl;
   if constexpr (INPL) {
     // no early return before the barrier: every wave reaches it
@@ -1360,6 +1341,10 @@ __device__ __forceinline__ u32x4 window16_small(const uint8_t* row, uint32_t len
 // 64 x 16 B (3.2 KiB).  Groups of more than 64 received packets run in chunks
 // of 64 with the same accumulator.
 constexpr int kFlatWaves = kBlock / 64;
+constexpr int kPairGroups = 2;  // ragged_multi_kernel: groups per wave
+constexpr int kPairWaves = kFlatWaves;  // ragged_multi_kernel: waves per block (4)
+constexpr int kRaggedU = 2;     // flat-window loops: iterations' loads in flight
+constexpr int kWindowPB = 16;   // ragged_window_kernel: load slots per trip
 constexpr int kParWin = 92;  // ceil(1452/16) = 91 windows (+1 spare)
 
 __device__ __forceinline__ uint32_t lane_id() {
@@ -1398,17 +1383,17 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
 // The accumulator is only ever accessed as uint32_t (plain and atomic): one
 // type, so the compiler cannot reorder the plain initialisation / final reads
 // across the atomic XORs on type-based alias grounds.
-//   ACC = 0: window t's four dwords at 4t .. 4t+3 (ds_xor_b32 x4; lanes on
-//            consecutive windows hit every 4th bank: 4-way conflicts)
-//   ACC = 1: component-major, dword c of window t at c*kParWin + t (lanes on
-//            consecutive windows hit consecutive banks: conflict-free)
-//   ACC = 2: interleaved, 2 x ds_xor_b64.  Its U = 4 build was wrong in ~1%
-//            of recover groups — not the atomics: that build's 64-bit funnel
-//            shift took its amount from the last VGPR; the
-//            funnels are 32-bit now.  Not used (no faster than ACC = 1).
-template <int ACC>
+// Component-major: dword c of window t at c*kParWin + t (ds_xor_b32 x4; lanes
+// on consecutive windows hit consecutive banks: conflict-free).
+// Layouts removed (template switch ACC, in git history at ace3ed3): window t's
+// four dwords at 4t .. 4t+3 (lanes on consecutive windows hit every 4th bank:
+// 4-way conflicts), and the same interleaved layout with 2 x ds_xor_b64, no
+// faster than component-major.  The latter's U = 4 build was wrong in ~1% of
+// recover groups -- not the atomics: that build's 64-bit funnel shift took its
+// amount from the last VGPR (profiles/round2/anomaly/); the
+// funnels are 32-bit now.
 __device__ __forceinline__ uint32_t acc_idx(uint32_t t, uint32_t c) {
-  return ACC == 1 ? c * (uint32_t)kParWin + t : 4u * t + c;
+  return c * (uint32_t)kParWin + t;
 }
 // SCOPE: the lanes that share the accumulator -- one wave (the per-group
 // body) or every wave of the block (ragged_block_kernel: 4 waves XOR into the
@@ -1418,30 +1403,21 @@ template <int SCOPE = __HIP_MEMORY_SCOPE_WAVEFRONT>
 __device__ __forceinline__ void lds_xor_u32(uint32_t* p, uint32_t v) {
   __hip_atomic_fetch_xor(p, v, __ATOMIC_RELAXED, SCOPE);
 }
-template <int ACC, int SCOPE = __HIP_MEMORY_SCOPE_WAVEFRONT>
+template <int SCOPE = __HIP_MEMORY_SCOPE_WAVEFRONT>
 __device__ __forceinline__ void lds_xor16(uint32_t* acc, uint32_t t, u32x4 v) {
-  if constexpr (ACC == 2) {
-    uint64_t* p = reinterpret_cast<uint64_t*>(acc + 4u * t);
-    __hip_atomic_fetch_xor(p, (uint64_t)v.x | ((uint64_t)v.y << 32), __ATOMIC_RELAXED, SCOPE);
-    __hip_atomic_fetch_xor(p + 1, (uint64_t)v.z | ((uint64_t)v.w << 32), __ATOMIC_RELAXED, SCOPE);
-  } else {
-    lds_xor_u32<SCOPE>(acc + acc_idx<ACC>(t, 0), v.x);
-    lds_xor_u32<SCOPE>(acc + acc_idx<ACC>(t, 1), v.y);
-    lds_xor_u32<SCOPE>(acc + acc_idx<ACC>(t, 2), v.z);
-    lds_xor_u32<SCOPE>(acc + acc_idx<ACC>(t, 3), v.w);
-  }
+  lds_xor_u32<SCOPE>(acc + acc_idx(t, 0), v.x);
+  lds_xor_u32<SCOPE>(acc + acc_idx(t, 1), v.y);
+  lds_xor_u32<SCOPE>(acc + acc_idx(t, 2), v.z);
+  lds_xor_u32<SCOPE>(acc + acc_idx(t, 3), v.w);
 }
-template <int ACC>
 __device__ __forceinline__ void lds_put16(uint32_t* acc, uint32_t t, u32x4 v) {
-  acc[acc_idx<ACC>(t, 0)] = v.x;
-  acc[acc_idx<ACC>(t, 1)] = v.y;
-  acc[acc_idx<ACC>(t, 2)] = v.z;
-  acc[acc_idx<ACC>(t, 3)] = v.w;
+  acc[acc_idx(t, 0)] = v.x;
+  acc[acc_idx(t, 1)] = v.y;
+  acc[acc_idx(t, 2)] = v.z;
+  acc[acc_idx(t, 3)] = v.w;
 }
-template <int ACC>
 __device__ __forceinline__ u32x4 lds_get16(const uint32_t* acc, uint32_t t) {
-  return u32x4{acc[acc_idx<ACC>(t, 0)], acc[acc_idx<ACC>(t, 1)], acc[acc_idx<ACC>(t, 2)],
-               acc[acc_idx<ACC>(t, 3)]};
+  return u32x4{acc[acc_idx(t, 0)], acc[acc_idx(t, 1)], acc[acc_idx(t, 2)], acc[acc_idx(t, 3)]};
 }
 
 // Bytes [16t, 16t+16) of a zero-padded packet (any len >= 1, 16t < len).
@@ -1529,7 +1505,7 @@ __device__ __forceinline__ void group_scalars(const RaggedArgs& a, uint64_t g, G
 // Vector part (needs the scalars).  Invalid groups load nothing.
 // ACCUM: the slot's row up to its old length is the "parity row"; a fresh slot
 // (old == 0) loads nothing of it.
-template <bool RECOVER, bool NT, bool ACCUM = false>
+template <bool RECOVER, bool ACCUM = false>
 __device__ __forceinline__ void group_vectors(const RaggedArgs& a, uint64_t g, uint32_t lane,
                                               GroupPrefetch& f,
                                               const AccumulateRaggedArgs* x = nullptr) {
@@ -1550,13 +1526,13 @@ __device__ __forceinline__ void group_vectors(const RaggedArgs& a, uint64_t g, u
   }
   if constexpr (RECOVER) {
     const uint8_t* prow = a.parity + a.parity_off[g];
-    if (16u * lane < f.plen) f.pw0 = packet_window<NT>(prow, f.plen, lane);
-    if (16u * (lane + 64u) < f.plen) f.pw1 = packet_window<NT>(prow, f.plen, lane + 64u);
+    if (16u * lane < f.plen) f.pw0 = packet_window<true>(prow, f.plen, lane);
+    if (16u * (lane + 64u) < f.plen) f.pw1 = packet_window<true>(prow, f.plen, lane + 64u);
   }
   if constexpr (ACCUM) {
     const uint8_t* prow = a.parity + f.dst_off;
-    if (16u * lane < f.old) f.pw0 = packet_window<NT>(prow, f.old, lane);
-    if (16u * (lane + 64u) < f.old) f.pw1 = packet_window<NT>(prow, f.old, lane + 64u);
+    if (16u * lane < f.old) f.pw0 = packet_window<true>(prow, f.old, lane);
+    if (16u * (lane + 64u) < f.old) f.pw1 = packet_window<true>(prow, f.old, lane + 64u);
   }
 }
 
@@ -1571,7 +1547,19 @@ __device__ __forceinline__ void group_vectors(const RaggedArgs& a, uint64_t g, u
 // ending at the length") overlaps the previous window's store with identical
 // bytes.  A group that latches an error returns before any store, to the row
 // or to its length; a group of no packets is a no-op.
-template <bool RECOVER, bool NT, int U, int ACC, bool BF = false, bool ACCUM = false>
+//
+// Loads and stores are nontemporal, kRaggedU iterations' loads are in flight
+// before the first XOR, the accumulator is component-major (acc_idx).
+// Variants measured and removed (template switches NT, U, ACC, BF of this
+// body and of ragged_pair_xor, in git history at ace3ed3; DESIGN.md §4,
+// profiles/round2/ragged_store/): default-policy (write-back) stores 0.500 /
+// 0.494 against 0.624 / 0.625; U = 1 / 2 / 3 / 4 encode 0.614 / 0.624 /
+// 0.629 / 0.625, recover 0.602 / 0.615 / 0.614 / 0.616, flat above 2
+// (tune_rw_diag7.txt); the other accumulator layouts, at acc_idx; a
+// branch-free XOR loop (BF: lanes past the last window XOR zero into window
+// `lane`) 0.615 / 0.602 against 0.625 / 0.616 strided, 0.618 / 0.587 against
+// 0.633 / 0.605 packed (tune_rw_diag6*.txt).
+template <bool RECOVER, bool ACCUM = false>
 __device__ __forceinline__ void ragged_group(const RaggedArgs& a, uint64_t g, uint32_t lane,
                                              const GroupPrefetch& f, uint32_t* par,
                                              uint64_t* head, u32x4* meta,
@@ -1594,8 +1582,8 @@ __device__ __forceinline__ void ragged_group(const RaggedArgs& a, uint64_t g, ui
     }
     if (k == 0u) return;  // nothing to fold this turn
     // accumulator := the slot's row (zero from its old length on)
-    lds_put16<ACC>(par, lane, f.pw0);
-    if (lane + 64u < kParWin) lds_put16<ACC>(par, lane + 64u, f.pw1);
+    lds_put16(par, lane, f.pw0);
+    if (lane + 64u < kParWin) lds_put16(par, lane + 64u, f.pw1);
   } else if constexpr (RECOVER) {
     if (m >= k) {
       if (lane == 0) atomicOr(a.err, kErrMissingIndex);
@@ -1606,14 +1594,15 @@ __device__ __forceinline__ void ragged_group(const RaggedArgs& a, uint64_t g, ui
       return;
     }
     // accumulator := the parity row (zero past plen), prefetched windows
-    lds_put16<ACC>(par, lane, f.pw0);
-    if (lane + 64u < kParWin) lds_put16<ACC>(par, lane + 64u, f.pw1);
+    lds_put16(par, lane, f.pw0);
+    if (lane + 64u < kParWin) lds_put16(par, lane + 64u, f.pw1);
   } else {
-    for (uint32_t t = lane; t < kParWin; t += 64u) lds_put16<ACC>(par, t, zero);
+    for (uint32_t t = lane; t < kParWin; t += 64u) lds_put16(par, t, zero);
   }
   const uint32_t kr = RECOVER ? k - 1u : k;  // received packets
   uint32_t lim = RECOVER ? plen : kMaxPacket;
   if constexpr (ACCUM) lim = x->lim;
+  constexpr int U = kRaggedU;
   uint32_t mx = 0;
   for (uint32_t c = 0; c < kr; c += 64u) {
     // packet table of this chunk: lane j = received packet c + j
@@ -1652,47 +1641,7 @@ __device__ __forceinline__ void ragged_group(const RaggedArgs& a, uint64_t g, ui
     const uint64_t below = lane == 63u ? ~0ull : ((2ull << lane) - 1ull);
     const uint32_t last = min(kr - c, 64u) - 1u;
     uint32_t before = 0;  // packet starts in earlier wave-iterations
-    if (BF && !wave_any(r < kr && len < 16u)) {
-      // Branch-free form: every lane loads and XORs on every iteration.  A
-      // lane past W loads its packet's last window and XORs ZERO into window
-      // `lane` (a no-op, conflict-free) — no exec-masked block, so the
-      // compiler cannot sink a load into one and wait on it right there.
-      for (uint32_t it = 0; it < nit; it += U) {
-        uint64_t M[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const uint64_t w = head[min(it + (uint32_t)u, (uint32_t)kParWin - 1u)];
-          M[u] = it + (uint32_t)u < nit ? w : 0ull;
-        }
-        u32x4 md[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const uint32_t pi = min(before + (uint32_t)__popcll(M[u] & below) - 1u, last);
-          before += (uint32_t)__popcll(M[u]);
-          md[u] = meta[pi];
-        }
-        u32x4 v[U];
-        uint32_t ts[U];  // window (bits 0-15) | shift (bits 16-19) | valid (bit 20)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const uint32_t fl = 64u * (it + (uint32_t)u) + lane;
-          const uint32_t win = 16u * (fl - md[u].w);
-          const bool full = win + 16u <= md[u].z;
-          v[u] = ld16t<NT>(a.bytes + (((uint64_t)md[u].y << 32) | md[u].x) +
-                           (full ? win : md[u].z - 16u));
-          const uint32_t sh = full ? 0u : min(win + 16u - md[u].z, 15u);
-          ts[u] = fl < W ? ((fl - md[u].w) | (sh << 16) | (1u << 20)) : lane;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          uint32_t keep = (ts[u] >> 20) ? 0xFFFFFFFFu : 0u;
-          // opaque to the optimiser: otherwise it proves the XOR of an idle
-          // lane to be 0, turns it into a branch and sinks the load into it
-          __asm__ volatile("" : "+v"(keep));
-          lds_xor16<ACC>(par, ts[u] & 0xFFFFu, shr_bytes_bf(v[u], (ts[u] >> 16) & 15u) & keep);
-        }
-      }
-    } else if (!BF && !wave_any(r < kr && len < 16u)) {
+    if (!wave_any(r < kr && len < 16u)) {
       // Every packet >= 16 B: every lane loads 16 in-packet bytes each
       // iteration (lanes past W re-read their packet's last window and drop
       // it), U iterations' loads in flight before the first XOR.
@@ -1717,14 +1666,14 @@ __device__ __forceinline__ void ragged_group(const RaggedArgs& a, uint64_t g, ui
           const uint32_t fl = 64u * (it + u) + lane;
           const uint32_t win = 16u * (fl - md[u].w);
           const bool full = win + 16u <= md[u].z;
-          v[u] = ld16t<NT>(a.bytes + (((uint64_t)md[u].y << 32) | md[u].x) +
+          v[u] = ld16t<true>(a.bytes + (((uint64_t)md[u].y << 32) | md[u].x) +
                            (full ? win : md[u].z - 16u));
           sh[u] = full ? 0u : min(win + 16u - md[u].z, 15u);
           tt[u] = fl < W ? fl - md[u].w : 0xFFFFFFFFu;
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          if (tt[u] != 0xFFFFFFFFu) lds_xor16<ACC>(par, tt[u], shr_bytes_bf(v[u], sh[u]));
+          if (tt[u] != 0xFFFFFFFFu) lds_xor16(par, tt[u], shr_bytes_bf(v[u], sh[u]));
       }
     } else {
       // Some packet below 16 B (rare): generic per-lane windows.
@@ -1736,7 +1685,7 @@ __device__ __forceinline__ void ragged_group(const RaggedArgs& a, uint64_t g, ui
         if (fl < W) {
           const u32x4 md = meta[pi];
           const uint32_t t = fl - md.w;
-          lds_xor16<ACC>(par, t, packet_window<false>(a.bytes + (((uint64_t)md.y << 32) | md.x),
+          lds_xor16(par, t, packet_window<false>(a.bytes + (((uint64_t)md.y << 32) | md.x),
                                                   md.z, t));
         }
       }
@@ -1755,16 +1704,16 @@ __device__ __forceinline__ void ragged_group(const RaggedArgs& a, uint64_t g, ui
     const uint32_t nw = (plen + 15u) >> 4;
     for (uint32_t t = lane; t < nw; t += 64u) {
       if (16u * t + 16u <= plen) {
-        st16t<NT>(dst + 16u * t, lds_get16<ACC>(par, t));
+        st16t<true>(dst + 16u * t, lds_get16(par, t));
       } else {
         // tail: the 16 bytes ending at plen, from windows t-1 and t
         const uint32_t o = plen - 16u * t;  // 1..15
-        const u32x4 lo = lds_get16<ACC>(par, t - 1u), hi = lds_get16<ACC>(par, t);
-        st16t<NT>(dst + plen - 16u, bytes16_at(lo, hi, o));
+        const u32x4 lo = lds_get16(par, t - 1u), hi = lds_get16(par, t);
+        st16t<true>(dst + plen - 16u, bytes16_at(lo, hi, o));
       }
     }
   } else if (lane < plen) {
-    dst[lane] = (uint8_t)(par[acc_idx<ACC>(0, lane >> 2)] >> (8u * (lane & 3u)));
+    dst[lane] = (uint8_t)(par[acc_idx(0, lane >> 2)] >> (8u * (lane & 3u)));
   }
 }
 
@@ -1810,17 +1759,17 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t lane, u
   return base + incl - x;
 }
 
-// PF (recover): the parity windows are loaded into the accumulators before the
-// packet table, so their round trip overlaps the table's (measured equal to
-// loading them after the scan, profiles/round3/ragged_block/block3.txt).
+// Recover and accumulate load their rows' windows into the accumulators before
+// the packet table, so their round trip overlaps the table's; kRaggedU
+// iterations' loads are in flight; a last window whose start is 16-B aligned
+// is loaded in place and masked (below); loads and stores are nontemporal.
 // DIAG (tools/tune only; bits): 1 = no parity stores (not exact); 2 = output
 // rows stored as whole 128-B lines (zeros past the parity length up to the
 // line end: the zero-padded parity of SURVEY.md Appendix A, for output slots
 // that have the room -- the write-granularity probe of round 6); 4 = no tail
 // logic (every window XORed whole, in place: the VALU probe of round 6, not
-// exact); 8 = parity stores through the caches (not nontemporal); 16 = payload
-// loads through the caches (both exact: the cache-policy probe of round 6);
-// bits 5-7 = P != 0: parity stores with explicit policy st16pol<P> (exact).
+// exact).  The three are what the open store-schedule item is measured with
+// (DESIGN.md §13).
 // LIST (recover, qfec_revive_ragged): group slot j of the block is not group
 // g0 + j with m = a.missing[g0 + j] but work-list entry step * GPB + j
 // (g << 8 | m) of a list of `count` entries; a.missing and a.n_groups are not
@@ -1844,15 +1793,29 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t lane, u
 // not take (an old length of 1..15, a group of no packets, any invalid field,
 // and the cases above) run the per-group body, which leaves the row and the
 // length of a group it rejects untouched.
-template <bool RECOVER, int WAVES, int GPB, int U = 2, bool PF = true, bool AL = true, int DIAG = 0,
-          bool LIST = false, bool ACCUM = false>
+//
+// Variants measured and removed (template switches U, PF, AL and DIAG bits 8,
+// 16 and 5-7, with the inline-assembly stores behind bits 5-7, in git history
+// at ace3ed3; DESIGN.md §4, rounds 3 and 6): U = 1 / 3 no better than 2
+// (profiles/round3/ragged_block/); the rows' windows loaded after the scan (PF
+// off) measured equal (profiles/round3/ragged_block/block3.txt); every last
+// window loaded as the 16 bytes ending at the packet end (AL off), the form
+// before the aligned payload arena; the round-6 cache-policy probe, all exact
+// (profiles/round6/tune_rblock_cache_r6p_{a16,a1}.txt, tune_rblock_pol_r6q.txt;
+// encode, arena layout) -- payload loads through the caches (16) 0.713 against
+// 0.736-0.739, parity stores through the caches (8) 0.530, stores with an
+// explicit policy (5-7) sc1 / sc0 sc1 0.531 / 0.532, nt sc1 / nt sc0 sc1
+// 0.656 / 0.665 against 0.691: the nontemporal loads and stores stay best.
+template <bool RECOVER, int WAVES, int GPB, int DIAG = 0, bool LIST = false, bool ACCUM = false>
 __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
                                                   const uint64_t* __restrict__ work = nullptr,
                                                   uint64_t count = 0, uint64_t step = 0,
                                                   const AccumulateRaggedArgs* x = nullptr) {
   static_assert(GPB >= 2 && GPB <= 64, "group slots are lanes of wave 0");
   static_assert(!LIST || RECOVER, "the work list is a receiver's");
-  static_assert(!ACCUM || (!RECOVER && !LIST && PF), "accumulate: the encode form, preloaded");
+  static_assert(!ACCUM || (!RECOVER && !LIST), "accumulate: the encode form");
+  static_assert((DIAG & ~7) == 0, "DIAG bits: 1 no stores, 2 whole-line stores, 4 no tail logic");
+  constexpr int U = kRaggedU;
   constexpr bool ROWIN = RECOVER || ACCUM;  // the accumulators start from a row
   constexpr uint32_t NT = 64u * WAVES;
   constexpr uint32_t NBLK = NT;        // 64-window blocks: CAPW = 64 NT windows
@@ -1929,7 +1892,7 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
   const uint32_t R = s_rb[GPB];
   bool fit = s_fit != 0u;
   // ---- 2. one received packet per lane
-  if (ROWIN && PF && fit) {
+  if (ROWIN && fit) {
     for (uint32_t q = tid; q < GPB * (uint32_t)kParWin; q += NT) {
       const uint32_t jq = q / (uint32_t)kParWin, t = q - jq * (uint32_t)kParWin;
       u32x4 w = {0u, 0u, 0u, 0u};
@@ -1940,7 +1903,7 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
       } else {
         if (jq < ng) w = parity_window_bf<true>(a.parity + s_poff[jq], s_pl[jq], t);
       }
-      lds_put16<1>(acc + jq * kAccWords, t, w);
+      lds_put16(acc + jq * kAccWords, t, w);
     }
   }
   uint32_t len = 0, offlo = 0, offhi = 0, j = 0;
@@ -1972,11 +1935,11 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
       uint32_t lm = 0;
       if constexpr (LIST) list_entry(work[g0 + jj], g, lm);  // jj < ng: below the count
       group_scalars<RECOVER, LIST, ACCUM>(a, g, f, lm, x);
-      group_vectors<RECOVER, true, ACCUM>(a, g, lane, f, x);
+      group_vectors<RECOVER, ACCUM>(a, g, lane, f, x);
       wave_lds_order();
-      ragged_group<RECOVER, true, 2, 1, false, ACCUM>(
-          a, g, lane, f, fb, reinterpret_cast<uint64_t*>(fb + 4u * kParWin),
-          reinterpret_cast<u32x4*>(fb + 6u * kParWin), x);
+      ragged_group<RECOVER, ACCUM>(a, g, lane, f, fb,
+                                   reinterpret_cast<uint64_t*>(fb + 4u * kParWin),
+                                   reinterpret_cast<u32x4*>(fb + 6u * kParWin), x);
       wave_lds_order();
     }
     return;
@@ -1986,15 +1949,12 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
     __hip_atomic_fetch_or(&s_head[S >> 6], 1ull << (S & 63u), __ATOMIC_RELAXED,
                           __HIP_MEMORY_SCOPE_WORKGROUP);
   }
-  // accumulators: the parity rows (recover) or zero (encode), windows of all groups
-  if (!(ROWIN && PF)) {
+  // accumulators of an encode: zero, windows of all groups
+  if (!ROWIN) {
     for (uint32_t q = tid; q < GPB * (uint32_t)kParWin; q += NT) {
       const uint32_t jq = q / (uint32_t)kParWin, t = q - jq * (uint32_t)kParWin;
-      u32x4 w = {0u, 0u, 0u, 0u};
-      if constexpr (RECOVER) {
-        if (jq < ng) w = parity_window_bf<true>(a.parity + s_poff[jq], s_pl[jq], t);
-      }
-      lds_put16<1>(acc + jq * kAccWords, t, w);
+      const u32x4 w = {0u, 0u, 0u, 0u};
+      lds_put16(acc + jq * kAccWords, t, w);
     }
   }
   __syncthreads();  // packet table, start mask, accumulators, parity lengths
@@ -2039,13 +1999,13 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
       const uint32_t win = 16u * (f - md[u].w);
       const bool full = win + 16u <= ln;
       const uint64_t at = (((uint64_t)md[u].y << 32) | md[u].x) + win;
-      // AL: a last window whose start is 16-B aligned (payloads on 16-B
+      // A last window whose start is 16-B aligned (payloads on 16-B
       // boundaries, the payload arena's layout) is loaded in place and its
       // bytes past the packet masked: an aligned 16-B load holding one packet
       // byte cannot leave that byte's page.  Otherwise the 16 bytes ending at
       // the packet end, shifted down.
-      inp[u] = full || (AL && win < ln && (at & 15u) == 0u) || (DIAG & 4);
-      v[u] = ld16t<(DIAG & 16) == 0>(a.bytes + (inp[u] ? at : at - win + ln - 16u));
+      inp[u] = full || (win < ln && (at & 15u) == 0u) || (DIAG & 4);
+      v[u] = ld16t<true>(a.bytes + (inp[u] ? at : at - win + ln - 16u));
       sh[u] = full ? 0u : min(win + 16u - ln, 15u);
       tt[u] = f < W ? (md[u].z >> 16) * kAccWords + (f - md[u].w) : 0xFFFFFFFFu;
     }
@@ -2055,15 +2015,13 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
         u32x4 w;
         if constexpr ((DIAG & 4) != 0) {
           w = v[u];
-        } else if constexpr (AL) {
+        } else {
           // in place: v & (ones >> sh); shifted: v >> sh (sh = 0 when full)
           const u32x4 ones = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
           const u32x4 m = shr_bytes_bf(inp[u] ? ones : v[u], sh[u]);
           w = inp[u] ? (m & v[u]) : m;
-        } else {
-          w = shr_bytes_bf(v[u], sh[u]);
         }
-        lds_xor16<1, __HIP_MEMORY_SCOPE_WORKGROUP>(acc, tt[u], w);
+        lds_xor16<__HIP_MEMORY_SCOPE_WORKGROUP>(acc, tt[u], w);
       }
   }
   __syncthreads();  // every lane's XORs done
@@ -2080,21 +2038,15 @@ __device__ __forceinline__ void ragged_block_body(const RaggedArgs& a,
     if ((DIAG & 1) && plen != 0xFFFFFu) continue;  // never a real length: no stores
     if (DIAG & 2) {  // whole lines: the accumulator is zero past plen
       const u32x4 z = {0u, 0u, 0u, 0u};
-      st16t<(DIAG & 8) == 0>(dst + 16u * t, t < (uint32_t)kParWin ? lds_get16<1>(ac, t) : z);
+      st16t<true>(dst + 16u * t, t < (uint32_t)kParWin ? lds_get16(ac, t) : z);
       continue;
     }
     if (16u * t + 16u <= plen) {
-      if constexpr ((DIAG >> 5) != 0)
-        st16pol<(DIAG >> 5)>(dst + 16u * t, lds_get16<1>(ac, t));
-      else
-        st16t<(DIAG & 8) == 0>(dst + 16u * t, lds_get16<1>(ac, t));
+      st16t<true>(dst + 16u * t, lds_get16(ac, t));
     } else {
       const uint32_t o = plen - 16u * t;  // 1..15
-      const u32x4 x = bytes16_at(lds_get16<1>(ac, t - 1u), lds_get16<1>(ac, t), o);
-      if constexpr ((DIAG >> 5) != 0)
-        st16pol<(DIAG >> 5)>(dst + plen - 16u, x);
-      else
-        st16t<(DIAG & 8) == 0>(dst + plen - 16u, x);
+      const u32x4 x = bytes16_at(lds_get16(ac, t - 1u), lds_get16(ac, t), o);
+      st16t<true>(dst + plen - 16u, x);
     }
   }
 }
@@ -2124,9 +2076,9 @@ __device__ __forceinline__ void ragged_signal_done(const RaggedArgs& a) {
 // The block kernel; with done_flag set (mapped batches of any size, round 4)
 // it signals completion like the small-batch kernel, so the host neither
 // stages the tables nor waits on an event.
-template <bool RECOVER, int WAVES, int GPB, int U = 2, bool PF = true, bool AL = true, int DIAG = 0>
+template <bool RECOVER, int WAVES, int GPB, int DIAG = 0>
 __global__ __launch_bounds__(64 * WAVES) void ragged_block_kernel(RaggedArgs a) {
-  ragged_block_body<RECOVER, WAVES, GPB, U, PF, AL, DIAG>(a);
+  ragged_block_body<RECOVER, WAVES, GPB, DIAG>(a);
   ragged_signal_done(a);
 }
 
@@ -2155,7 +2107,7 @@ __global__ __launch_bounds__(64 * WAVES) void revive_ragged_kernel(
   const uint64_t count = totals[kGroupRevived];
   const uint64_t nstep = (count + GPB - 1) / GPB;
   for (uint64_t step = blockIdx.x; step < nstep; step += gridDim.x) {
-    ragged_block_body<true, WAVES, GPB, 2, true, true, 0, true>(a, work, count, step);
+    ragged_block_body<true, WAVES, GPB, 0, true>(a, work, count, step);
     __syncthreads();  // the step's LDS reads are done before the next step's writes
   }
 }
@@ -2174,7 +2126,7 @@ __global__ __launch_bounds__(64 * WAVES) void accumulate_ragged_kernel(Accumulat
   a.out = v.acc;
   a.n_groups = v.n_groups;
   a.err = v.err;
-  ragged_block_body<false, WAVES, GPB, 2, true, true, 0, false, true>(a, nullptr, 0, 0, &v);
+  ragged_block_body<false, WAVES, GPB, 0, false, true>(a, nullptr, 0, 0, &v);
 }
 
 // Lane j's 64-bit value as a scalar (j wave-uniform).
@@ -2286,18 +2238,25 @@ static_assert((kMaxPacket + 15u) / 16u + 2u <= 128u, "two chunks per lane cover 
 
 // Two groups per wave (round 2's product kernel; since round 6 the kernel of
 // large batches whose groups are small -- launch_ragged's shape-aware choice,
-// below): GPW consecutive groups in
+// below): kPairGroups = 2 consecutive groups in
 // ONE flat window space — their received packets fill the 64-lane packet
 // table together — so the per-group load chain (group pointer -> packet table
 // -> packet bytes), which parks the one-group waves for 70% of their cycles
 // (SQ_WAIT_ANY, profiles/round1/sq_stalls_fec_pq.txt), and the partially idle
-// last iteration are paid once per GPW groups.  Groups that do not fit (more
+// last iteration are paid once per pair.  Groups that do not fit (more
 // than 64 received packets together, a packet below 16 B, any invalid field)
 // run the per-group body above with its exact error semantics.  Measured
 // +1.0-1.6% encode and recover over one group per wave in three interleaved
 // A/B runs (tune_multi_t2.txt, ragged_slots_p*.txt, tune_multi_sp.txt);
-// three groups per wave overflow the table too often (-10%).  tools/tune runs
-// it with GPW = 2.
+// three groups per wave overflow the table too often (-10%).
+//
+// Variants measured and removed (template switches NT, GPW, U, WAVES, BF and
+// the parity-window form, in git history at ace3ed3; NT, U and BF as for
+// ragged_group above): U = 1 / 3 -1.7% / +0.7%, 2 or 8 waves per block
+// -0.6% / -0.5...-2.6% (profiles/round1/tune_multi_mu.txt); the recover's
+// parity windows loaded under lane masks (round 2's form) recover 0.608
+// against 0.615 strided, 0.593 against 0.605 packed
+// (profiles/round2/ragged_store/tune_rw_diag5*.txt).
 
 template <int N, typename T>
 __device__ __forceinline__ T sel_n(const T (&v)[N], uint32_t j) {
@@ -2307,25 +2266,25 @@ __device__ __forceinline__ T sel_n(const T (&v)[N], uint32_t j) {
   return r;
 }
 
-// GPW groups g0 .. g0+ng-1 of one wave, up to their XOR into the LDS
-// accumulators `par` (GPW x kAccWords).  Returns false when the groups took
+// The kPairGroups groups g0 .. g0+ng-1 of one wave, up to their XOR into the
+// LDS accumulators `par` (kPairGroups x kAccWords).  Returns false when the groups took
 // the per-group body (odd packets, invalid fields, > 64 received packets):
 // then their outputs are already stored; true: ragged_pair_store writes them
 // from `par` with lengths pl[] at offsets doff[].
 
-template <bool RECOVER, bool NT, int GPW, int U, bool BF, bool PBF = true>
+template <bool RECOVER>
 __device__ __forceinline__ bool ragged_pair_xor(const RaggedArgs& a, uint64_t g0, uint32_t ng,
                                                 uint32_t lane, uint32_t* par, uint64_t* head,
-                                                u32x4* meta, uint32_t (&pl)[GPW],
-                                                uint64_t (&doff)[GPW]) {
-  constexpr int ACC = 1;
+                                                u32x4* meta, uint32_t (&pl)[kPairGroups],
+                                                uint64_t (&doff)[kPairGroups]) {
+  constexpr int U = kRaggedU;
   // wave-uniform group scalars
-  uint32_t kb[GPW + 1], rb[GPW + 1], mm[GPW];
+  uint32_t kb[kPairGroups + 1], rb[kPairGroups + 1], mm[kPairGroups];
   const uint32_t P0 = a.grp_ptr[g0];
   bool ok = true;
   kb[0] = rb[0] = 0;
 #pragma unroll
-  for (int j = 0; j < GPW; ++j) {
+  for (int j = 0; j < kPairGroups; ++j) {
     uint32_t k = 0, m = 0xFFFFFFFFu, p = 0;
     uint64_t d = 0;
     if ((uint32_t)j < ng) {
@@ -2346,20 +2305,20 @@ __device__ __forceinline__ bool ragged_pair_xor(const RaggedArgs& a, uint64_t g0
     pl[j] = p;
     doff[j] = d;
   }
-  const uint32_t R = rb[GPW];
+  const uint32_t R = rb[kPairGroups];
   ok = ok && R <= 64u;
 
   // lane r: received packet r of the wave's groups
   uint32_t jl = 0, base = 0, kbase = 0, ml = 0xFFFFFFFFu, lim = kMaxPacket;
 #pragma unroll
-  for (int j = 1; j < GPW; ++j) {
+  for (int j = 1; j < kPairGroups; ++j) {
     const bool in = lane >= rb[j];
     jl += in ? 1u : 0u;
     base = in ? rb[j] : base;
     kbase = in ? kb[j] : kbase;
   }
-  ml = sel_n<GPW>(mm, jl);
-  if constexpr (RECOVER) lim = sel_n<GPW>(pl, jl);
+  ml = sel_n<kPairGroups>(mm, jl);
+  if constexpr (RECOVER) lim = sel_n<kPairGroups>(pl, jl);
   uint32_t len = 0, offlo = 0, offhi = 0;
   if (ok && lane < R) {
     const uint32_t i = lane - base;
@@ -2372,7 +2331,7 @@ __device__ __forceinline__ bool ragged_pair_xor(const RaggedArgs& a, uint64_t g0
   // accumulators: the parity rows (recover) or zero (encode)
   if (ok) {
 #pragma unroll
-    for (int j = 0; j < GPW; ++j) {
+    for (int j = 0; j < kPairGroups; ++j) {
       uint32_t* acc = par + j * kAccWords;
       if constexpr (RECOVER) {
         const uint8_t* prow = a.parity + ((uint32_t)j < ng ? a.parity_off[g0 + j] : 0ull);
@@ -2383,18 +2342,15 @@ __device__ __forceinline__ bool ragged_pair_xor(const RaggedArgs& a, uint64_t g0
         // pair takes this path (ok); the branch is wave-uniform.
         const u32x4 zero = {0u, 0u, 0u, 0u};
         u32x4 w0 = zero, w1 = zero;
-        if (!PBF) {  // the round-2 form (A/B reference, tools/tune/ragged_exp.inc)
-          if (16u * lane < plj) w0 = packet_window<NT>(prow, plj, lane);
-          if (16u * (lane + 64u) < plj) w1 = packet_window<NT>(prow, plj, lane + 64u);
-        } else if (plj >= 16u) {
-          w0 = parity_window_bf<NT>(prow, plj, lane);
-          w1 = parity_window_bf<NT>(prow, plj, lane + 64u);
+        if (plj >= 16u) {
+          w0 = parity_window_bf<true>(prow, plj, lane);
+          w1 = parity_window_bf<true>(prow, plj, lane + 64u);
         }
-        lds_put16<ACC>(acc, lane, w0);
-        if (lane + 64u < kParWin) lds_put16<ACC>(acc, lane + 64u, w1);
+        lds_put16(acc, lane, w0);
+        if (lane + 64u < kParWin) lds_put16(acc, lane + 64u, w1);
       } else {
         const u32x4 zero = {0u, 0u, 0u, 0u};
-        for (uint32_t t = lane; t < kParWin; t += 64u) lds_put16<ACC>(acc, t, zero);
+        for (uint32_t t = lane; t < kParWin; t += 64u) lds_put16(acc, t, zero);
       }
     }
   }
@@ -2404,9 +2360,9 @@ __device__ __forceinline__ bool ragged_pair_xor(const RaggedArgs& a, uint64_t g0
     for (uint32_t j = 0; j < ng; ++j) {
       GroupPrefetch f;
       group_scalars<RECOVER>(a, g0 + j, f);
-      group_vectors<RECOVER, NT>(a, g0 + j, lane, f);
+      group_vectors<RECOVER>(a, g0 + j, lane, f);
       wave_lds_order();
-      ragged_group<RECOVER, NT, U, ACC, BF>(a, g0 + j, lane, f, par, head, meta);
+      ragged_group<RECOVER>(a, g0 + j, lane, f, par, head, meta);
       wave_lds_order();
     }
     return false;
@@ -2446,27 +2402,17 @@ __device__ __forceinline__ bool ragged_pair_xor(const RaggedArgs& a, uint64_t g0
       const uint32_t ln = md[u].z & 0xFFFFu;
       const uint32_t win = 16u * (fl - md[u].w);
       const bool full = win + 16u <= ln;
-      v[u] = ld16t<NT>(a.bytes + (((uint64_t)md[u].y << 32) | md[u].x) + (full ? win : ln - 16u));
+      v[u] = ld16t<true>(a.bytes + (((uint64_t)md[u].y << 32) | md[u].x) + (full ? win : ln - 16u));
       sh[u] = full ? 0u : min(win + 16u - ln, 15u);
       tt[u] = fl < W ? (md[u].z >> 16) * kAccWords + (fl - md[u].w) : 0xFFFFFFFFu;
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if constexpr (BF) {
-        // branch-free: a lane past W XORs ZERO into window `lane` of the first
-        // accumulator (a no-op, conflict-free), so no load or LDS atomic sits
-        // in an exec-masked block
-        uint32_t keep = tt[u] != 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u;
-        __asm__ volatile("" : "+v"(keep));
-        lds_xor16<ACC>(par, tt[u] != 0xFFFFFFFFu ? tt[u] : lane, shr_bytes_bf(v[u], sh[u]) & keep);
-      } else if (tt[u] != 0xFFFFFFFFu) {
-        lds_xor16<ACC>(par, tt[u], shr_bytes_bf(v[u], sh[u]));
-      }
-    }
+    for (int u = 0; u < U; ++u)
+      if (tt[u] != 0xFFFFFFFFu) lds_xor16(par, tt[u], shr_bytes_bf(v[u], sh[u]));
   }
   if constexpr (!RECOVER) {
 #pragma unroll
-    for (int j = 0; j < GPW; ++j) {
+    for (int j = 0; j < kPairGroups; ++j) {
       pl[j] = wave_max11(lane < R && jl == (uint32_t)j ? len : 0u);
       if (lane == 0 && (uint32_t)j < ng) a.parity_len_out[g0 + j] = (uint16_t)pl[j];
     }
@@ -2474,57 +2420,56 @@ __device__ __forceinline__ bool ragged_pair_xor(const RaggedArgs& a, uint64_t g0
   return true;
 }
 
-template <bool NT, int GPW>
 __device__ __forceinline__ void ragged_pair_store(const RaggedArgs& a, uint32_t ng, uint32_t lane,
-                                                  const uint32_t* par, const uint32_t (&pl)[GPW],
-                                                  const uint64_t (&doff)[GPW]) {
-  constexpr int ACC = 1;
+                                                  const uint32_t* par,
+                                                  const uint32_t (&pl)[kPairGroups],
+                                                  const uint64_t (&doff)[kPairGroups]) {
   wave_lds_order();  // every lane's XORs done
   // write-out, flattened over the groups' output windows
-  uint32_t ob[GPW + 1];
+  uint32_t ob[kPairGroups + 1];
   ob[0] = 0;
 #pragma unroll
-  for (int j = 0; j < GPW; ++j) ob[j + 1] = ob[j] + ((uint32_t)j < ng ? (pl[j] + 15u) >> 4 : 0u);
-  const uint32_t NW = ob[GPW];
+  for (int j = 0; j < kPairGroups; ++j)
+    ob[j + 1] = ob[j] + ((uint32_t)j < ng ? (pl[j] + 15u) >> 4 : 0u);
+  const uint32_t NW = ob[kPairGroups];
   for (uint32_t q = lane; q < NW; q += 64u) {
     uint32_t jq = 0, qb = 0;
 #pragma unroll
-    for (int j = 1; j < GPW; ++j) {
+    for (int j = 1; j < kPairGroups; ++j) {
       const bool in = q >= ob[j];
       jq += in ? 1u : 0u;
       qb = in ? ob[j] : qb;
     }
     const uint32_t t = q - qb;
-    const uint32_t plen = sel_n<GPW>(pl, jq);
-    uint8_t* dst = a.out + sel_n<GPW>(doff, jq);
+    const uint32_t plen = sel_n<kPairGroups>(pl, jq);
+    uint8_t* dst = a.out + sel_n<kPairGroups>(doff, jq);
     const uint32_t* acc = par + jq * kAccWords;
     if (16u * t + 16u <= plen) {
-      st16t<NT>(dst + 16u * t, lds_get16<ACC>(acc, t));
+      st16t<true>(dst + 16u * t, lds_get16(acc, t));
     } else {
       const uint32_t o = plen - 16u * t;  // 1..15
-      const u32x4 lo = lds_get16<ACC>(acc, t - 1u), hi = lds_get16<ACC>(acc, t);
-      st16t<NT>(dst + plen - 16u, bytes16_at(lo, hi, o));
+      const u32x4 lo = lds_get16(acc, t - 1u), hi = lds_get16(acc, t);
+      st16t<true>(dst + plen - 16u, bytes16_at(lo, hi, o));
     }
   }
 }
 
 // (with done_flag set -- a direct mapped batch -- it signals completion like
 // the block kernel: every wave reaches ragged_signal_done)
-template <bool RECOVER, bool NT, int GPW, int U = 2, int WAVES = kFlatWaves, bool BF = false>
-__global__ __launch_bounds__(64 * WAVES) void ragged_multi_kernel(RaggedArgs a) {
-  __shared__ uint32_t s_par[WAVES][GPW * kAccWords];
-  __shared__ uint64_t s_head[WAVES][kParWin];
-  __shared__ u32x4 s_meta[WAVES][64];
+template <bool RECOVER>
+__global__ __launch_bounds__(64 * kPairWaves) void ragged_multi_kernel(RaggedArgs a) {
+  __shared__ uint32_t s_par[kPairWaves][kPairGroups * kAccWords];
+  __shared__ uint64_t s_head[kPairWaves][kParWin];
+  __shared__ u32x4 s_meta[kPairWaves][64];
   const uint32_t lane = lane_id();
   const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t g0 = ((uint64_t)blockIdx.x * WAVES + wv) * GPW;
+  const uint64_t g0 = ((uint64_t)blockIdx.x * kPairWaves + wv) * kPairGroups;
   if (g0 < a.n_groups) {  // wave-uniform
-    const uint32_t ng = (uint32_t)min<uint64_t>((uint64_t)GPW, a.n_groups - g0);
-    uint32_t pl[GPW];
-    uint64_t doff[GPW];
-    if (ragged_pair_xor<RECOVER, NT, GPW, U, BF>(a, g0, ng, lane, s_par[wv], s_head[wv],
-                                                  s_meta[wv], pl, doff))
-      ragged_pair_store<NT, GPW>(a, ng, lane, s_par[wv], pl, doff);
+    const uint32_t ng = (uint32_t)min<uint64_t>((uint64_t)kPairGroups, a.n_groups - g0);
+    uint32_t pl[kPairGroups];
+    uint64_t doff[kPairGroups];
+    if (ragged_pair_xor<RECOVER>(a, g0, ng, lane, s_par[wv], s_head[wv], s_meta[wv], pl, doff))
+      ragged_pair_store(a, ng, lane, s_par[wv], pl, doff);
   }
   ragged_signal_done(a);
 }
@@ -2536,7 +2481,11 @@ __global__ __launch_bounds__(64 * WAVES) void ragged_multi_kernel(RaggedArgs a) 
 // group's time is its count of dependent round trips, not bandwidth.  (On
 // large device-resident batches it is 0.77x ragged_multi_kernel: the
 // texture-address unit costs ~64 cycles per 64-lane load whatever its useful
-// lanes; tools/tune/tune_rw.hip)
+// lanes; profiles/round2/tune_rw_window*.txt, DESIGN.md §4 -- the A/B driver,
+// tools/tune/tune_rw.hip, is in git history at ace3ed3.)  Loads and stores
+// are nontemporal and kWindowPB = 16 slots are in flight: the library never
+// launched another value of the kernel's switches NT and PB (in git history
+// at ace3ed3; window_group keeps PB and NP, which the service varies).
 // One wave per group, lane l owns the parity
 // windows at bytes w0 = min(16l, plen-16) and w1 = min(16(l+64), plen-16) —
 // the fixed-shape kernel's mapping (the last window ends exactly at plen and
@@ -2575,7 +2524,7 @@ struct WinOut {
   bool red;  // partials left in red0 / red1 (false: finished, or NP == 1)
 };
 
-template <bool RECOVER, bool NT, int PB, int NP = 1>
+template <bool RECOVER, int PB, int NP = 1>
 __device__ __forceinline__ WinOut window_group(const RaggedArgs& a, uint64_t g, uint32_t lane,
                                                uint32_t* s_par, uint64_t* s_head, u32x4* s_meta,
                                                uint32_t part = 0, u32x4* red0 = nullptr,
@@ -2620,8 +2569,8 @@ __device__ __forceinline__ WinOut window_group(const RaggedArgs& a, uint64_t g, 
     w1 = min(16u * (lane + 64u), plen - 16u);
     if (pt == 0u) {
       const uint8_t* prow = a.parity + par_off;
-      acc0 = ld16t<NT>(prow + w0);
-      if (plen > 1024u) acc1 = ld16t<NT>(prow + w1);
+      acc0 = ld16t<true>(prow + w0);
+      if (plen > 1024u) acc1 = ld16t<true>(prow + w1);
     }
   }
   const uint32_t lim = RECOVER ? plen : kMaxPacket;
@@ -2629,8 +2578,8 @@ __device__ __forceinline__ WinOut window_group(const RaggedArgs& a, uint64_t g, 
     if (pt == 0u) {
       GroupPrefetch f;
       group_scalars<RECOVER>(a, g, f);
-      group_vectors<RECOVER, NT>(a, g, lane, f);
-      ragged_group<RECOVER, NT, 2, 1>(a, g, lane, f, s_par, s_head, s_meta);
+      group_vectors<RECOVER>(a, g, lane, f);
+      ragged_group<RECOVER>(a, g, lane, f, s_par, s_head, s_meta);
     }
     return WinOut{nullptr, 0u, 0u, 0u, false};
   }
@@ -2704,7 +2653,7 @@ __device__ __forceinline__ WinOut window_group(const RaggedArgs& a, uint64_t g, 
       const __amdgpu_buffer_rsrc_t rs =
           __builtin_amdgcn_make_buffer_rsrc((void*)(a.bytes + o), 0, (int)li[u], 0x00020000);
       const uint32_t w = j >= kr ? w1 : w0;
-      v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)min(w, li[u] - 16u), 0, NT ? 2 : 0);
+      v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)min(w, li[u] - 16u), 0, 2);  // nt
       // the first chunk in source order: each slot's descriptor right before
       // its load (hoisting them all holds 4 SGPRs a slot: spills) and every
       // load before any use (the scheduler otherwise interleaves the uses and
@@ -2734,14 +2683,14 @@ __device__ __forceinline__ WinOut window_group(const RaggedArgs& a, uint64_t g, 
     red1[pt * 64u + lane] = acc1;
     return WinOut{dst, w0, w1, nwin, true};
   }
-  if (lane < nwin) st16t<NT>(dst + w0, acc0);
-  if (lane + 64u < nwin) st16t<NT>(dst + w1, acc1);
+  if (lane < nwin) st16t<true>(dst + w0, acc0);
+  if (lane + 64u < nwin) st16t<true>(dst + w1, acc1);
   return WinOut{nullptr, 0u, 0u, 0u, false};
 }
 
 // (one workgroup per 4 groups of a small batch: occupancy is no object; the
 // default 4-waves-per-SIMD target left the recover body 128 VGPRs and spilled)
-template <bool RECOVER, bool NT, int PB>
+template <bool RECOVER>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 2))) void ragged_window_kernel(
     RaggedArgs a) {
   __shared__ uint32_t s_par[kFlatWaves][4 * kParWin];
@@ -2750,7 +2699,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 2))) 
   const uint32_t lane = lane_id();
   const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint64_t g = (uint64_t)blockIdx.x * kFlatWaves + wv;
-  if (g < a.n_groups) window_group<RECOVER, NT, PB>(a, g, lane, s_par[wv], s_head[wv], s_meta[wv]);
+  if (g < a.n_groups)
+    window_group<RECOVER, kWindowPB>(a, g, lane, s_par[wv], s_head[wv], s_meta[wv]);
   ragged_signal_done(a);
 }
 
@@ -2860,14 +2810,14 @@ __global__ __launch_bounds__(64 * kSvcWaves) void ragged_service_kernel(
       WinOut o{nullptr, 0u, 0u, 0u, false};
       if (q < n) {
         if (n == 1u)
-          o = J.recover ? window_group<true, true, kSvcPB, kSvcWaves>(
+          o = J.recover ? window_group<true, kSvcPB, kSvcWaves>(
                               a, 0, lane, s_par[wv], s_head[wv], s_meta[wv], part, r0, r1)
-                        : window_group<false, true, kSvcPB, kSvcWaves>(
+                        : window_group<false, kSvcPB, kSvcWaves>(
                               a, 0, lane, s_par[wv], s_head[wv], s_meta[wv], part, r0, r1);
         else
-          o = J.recover ? window_group<true, true, kSvcPB, 4>(
+          o = J.recover ? window_group<true, kSvcPB, 4>(
                               a, q, lane, s_par[wv], s_head[wv], s_meta[wv], part, r0, r1)
-                        : window_group<false, true, kSvcPB, 4>(
+                        : window_group<false, kSvcPB, 4>(
                               a, q, lane, s_par[wv], s_head[wv], s_meta[wv], part, r0, r1);
       }
       __syncthreads();
@@ -2881,9 +2831,9 @@ __global__ __launch_bounds__(64 * kSvcWaves) void ragged_service_kernel(
     } else {
       for (uint64_t g = split ? (uint64_t)wv * kSvcWgs + wg : wv; g < n; g += step) {
         if (J.recover)
-          window_group<true, true, kSvcPBw>(a, g, lane, s_par[wv], s_head[wv], s_meta[wv]);
+          window_group<true, kSvcPBw>(a, g, lane, s_par[wv], s_head[wv], s_meta[wv]);
         else
-          window_group<false, true, kSvcPBw>(a, g, lane, s_par[wv], s_head[wv], s_meta[wv]);
+          window_group<false, kSvcPBw>(a, g, lane, s_par[wv], s_head[wv], s_meta[wv]);
         if (tid == 0 && g == 0) st[2] = wall_clock64();
       }
     }
@@ -3300,13 +3250,13 @@ hipError_t launch_fixed_k(const FixedArgs& a, uint32_t C, uint32_t gpb, uint64_t
   switch (a.k) {
 #define QFEC_K_CASE(KV)                                                                       \
   case KV:                                                                                     \
-    hipLaunchKernelGGL((fixed_xor_kernel<KV, RECOVER, NT, SM, false, INPL>),                   \
+    hipLaunchKernelGGL((fixed_xor_kernel<KV, RECOVER, NT, SM, INPL>),                          \
                        dim3((uint32_t)blocks), dim3(kBlock), 0, s, a, C, gpb);                 \
     break;
     QFEC_K_ALL(QFEC_K_CASE)
 #undef QFEC_K_CASE
     default:
-      hipLaunchKernelGGL((fixed_xor_kernel<0, RECOVER, NT, SM, false, INPL>),
+      hipLaunchKernelGGL((fixed_xor_kernel<0, RECOVER, NT, SM, INPL>),
                          dim3((uint32_t)blocks), dim3(kBlock), 0, s, a, C, gpb);
   }
   return hipGetLastError();
@@ -3702,12 +3652,14 @@ hipError_t launch_ragged(const RaggedArgs& a0, bool recover, hipStream_t s, bool
     const uint64_t blocks = (a.n_groups + gpb - 1) / gpb;
     // (two groups per wave x 4 waves: the block kernel's 8 groups per block)
     static_assert(2 * kFlatWaves == kRaggedBlockGroups, "one grid for both kernels");
+    static_assert(kPairGroups * kPairWaves == kRaggedBlockGroups && 64 * kPairWaves == kBlock,
+                  "the pair kernel's block");
     if (small_groups) {
       if (recover)
-        hipLaunchKernelGGL((ragged_multi_kernel<true, true, 2>), dim3((uint32_t)blocks),
+        hipLaunchKernelGGL((ragged_multi_kernel<true>), dim3((uint32_t)blocks),
                            dim3(kBlock), 0, s, a);
       else
-        hipLaunchKernelGGL((ragged_multi_kernel<false, true, 2>), dim3((uint32_t)blocks),
+        hipLaunchKernelGGL((ragged_multi_kernel<false>), dim3((uint32_t)blocks),
                            dim3(kBlock), 0, s, a);
     } else if (recover) {
       hipLaunchKernelGGL((ragged_block_kernel<true, kRaggedBlockWaves, kRaggedBlockGroups>),
@@ -3726,13 +3678,14 @@ hipError_t launch_ragged_latency(const RaggedArgs& a, bool recover, hipStream_t 
   if (a.n_groups == 0) return hipSuccess;
   if (a.n_groups > kMaxBlocks256) return hipErrorInvalidValue;  // small batches only
   const uint64_t blocks = (a.n_groups + kFlatWaves - 1) / kFlatWaves;
-  // all of a group's loads in flight at once: 16 load slots per lane covers
-  // up to 16 received packets (+ their second windows) in one round trip
+  // all of a group's loads in flight at once: kWindowPB = 16 load slots per
+  // lane cover up to 16 received packets (+ their second windows) in one round
+  // trip
   if (recover)
-    hipLaunchKernelGGL((ragged_window_kernel<true, true, 16>), dim3((uint32_t)blocks),
+    hipLaunchKernelGGL((ragged_window_kernel<true>), dim3((uint32_t)blocks),
                        dim3(kBlock), 0, s, a);
   else
-    hipLaunchKernelGGL((ragged_window_kernel<false, true, 16>), dim3((uint32_t)blocks),
+    hipLaunchKernelGGL((ragged_window_kernel<false>), dim3((uint32_t)blocks),
                        dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }

@@ -113,7 +113,7 @@ def test_ragged_synth_vs_oracle(ctx, align, slot):
     ks, ptr, ln, off = synth_batch(n, g0=77, align=align)
     total = int(off[-1] + ln[-1])
     # gaps between aligned payloads hold 0xA5: a last window loaded in place
-    # (ragged_block_kernel AL) must mask them, not rely on zeros
+    # (ragged_block_kernel's aligned last windows) must mask them, not rely on zeros
     data_d = torch.full((total,), 0xA5, dtype=torch.uint8, device=DEV)
     ctx.synth_ragged(data_d, dview(off), dview(ln), dview(ptr), 77, n, Q.SEED_RAGGED)
     ctx.sync()

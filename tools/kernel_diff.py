@@ -16,6 +16,17 @@ renumbers those and changes nothing else.  Also compared, from each kernel's
 .amdhsa_kernel block: next_free_vgpr, next_free_sgpr, group_segment_fixed_size,
 private_segment_fixed_size and kernarg_size.
 
+A change that drops template parameters renames its kernels.  Then
+
+    python tools/kernel_diff.py --renames MAP parent.s head.s
+
+renames the first file's kernels before pairing: each line of MAP holds two
+mangled symbols, `old new`.  (No instruction mentions a kernel symbol; the
+directives that close a kernel's stream name its own, and are renamed with
+it.)  An `old` that is no kernel of the first file, or two lines with the same
+`old` or the same `new`, end the run with exit status 2: a stale map must not
+hide a missing kernel.
+
 Prints the kernel counts, the symbols only one side has, the symbols whose
 stream or resources differ.  Exit status 1 if anything differs.  CPU only.
 """
@@ -53,11 +64,52 @@ def resources(path):
     return out
 
 
+def _die(msg):
+    print(msg, file=sys.stderr)
+    sys.exit(2)
+
+
+def read_renames(path, kernels):
+    """{old: new} from a map file; exits 2 on a line that could hide a kernel."""
+    ren = {}
+    for n, line in enumerate(open(path), 1):
+        f = line.split()
+        if not f:
+            continue
+        if len(f) != 2:
+            _die(f"{path}:{n}: expected `old new`, got {len(f)} fields")
+        old, new = f
+        if old not in kernels:
+            _die(f"{path}:{n}: {old} is not a kernel of the first file")
+        if old in ren:
+            _die(f"{path}:{n}: {old} is renamed twice")
+        if new in ren.values():
+            _die(f"{path}:{n}: two kernels are renamed to {new}")
+        ren[old] = new
+    return ren
+
+
 def main(argv):
+    renames = None
+    if len(argv) >= 3 and argv[1] == "--renames":
+        renames, argv = argv[2], argv[:1] + argv[3:]
     if len(argv) != 3:
         sys.exit(__doc__)
     a, b = argv[1], argv[2]
     sa, sb, ra, rb = streams(a), streams(b), resources(a), resources(b)
+    if renames is not None:
+        ren = read_renames(renames, sa)
+        # a rename onto a kernel that keeps its own name would merge the two
+        for old, new in ren.items():
+            if new in sa and new not in ren:
+                _die(f"{renames}: {old} is renamed to {new}, a kernel of the first file")
+        # (every old name leaves before a new one arrives: a new name may be
+        # another line's old one; the directives at a stream's end name the
+        # kernel's own symbol)
+        moved = [(old, new, sa.pop(old), ra.pop(old, {})) for old, new in ren.items()]
+        for old, new, stream, figures in moved:
+            sa[new] = [line.replace(old, new) for line in stream]
+            ra[new] = figures
     print(f"{a}: {len(sa)} kernels")
     print(f"{b}: {len(sb)} kernels")
     only_a, only_b = sorted(set(sa) - set(sb)), sorted(set(sb) - set(sa))

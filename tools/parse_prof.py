@@ -20,8 +20,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def kind(name):
-    """fixed_xor_kernel<K, RECOVER, NT, SM> / phase_xor_kernel<K, RECOVER, ...> (the
-    product's fixed-shape kernels: one-pass and phased) / ragged_block_kernel<RECOVER, ...> (round 3; ragged_multi_kernel before)."""
+    """fixed_xor_kernel<K, RECOVER, NT, SM, INPL> / phase_xor_kernel<K, RECOVER, ...>
+    (the product's fixed-shape kernels: one-pass and phased) /
+    ragged_block_kernel<RECOVER, WAVES, GPB, DIAG> (round 3) and
+    ragged_multi_kernel<RECOVER> (large batches of small groups; the product
+    before round 3).  Older profiles name these with more template arguments
+    and a ragged_xor_kernel: only the first ones are read."""
     m = re.search(r"(?:fixed|phase)_xor_kernel<(-?\d+), (true|false)", name)
     if m:
         return "recover" if m.group(2) == "true" else "encode"

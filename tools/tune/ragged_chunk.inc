@@ -99,7 +99,6 @@ __global__ __launch_bounds__(kRcThreads) void ragged_chunk_kernel(RaggedArgs a, 
                                                                   uint32_t* psync, uint32_t* phost,
                                                                   uint64_t* tstamp = nullptr) {
   static_assert(GP % kRcGPS == 0 && GP <= kRcThreads, "chunk shape");
-  constexpr int ACC = 1;
   constexpr uint32_t kSlot = 4u * kParWin;  // accumulator words per group (= kAccWords)
   __shared__ uint32_t s_acc[GP * kSlot];
   __shared__ u32x4 s_pk[kRcMaxPk];  // {off lo, off hi, len | slot << 16, first window S}
@@ -199,7 +198,7 @@ __global__ __launch_bounds__(kRcThreads) void ragged_chunk_kernel(RaggedArgs a, 
           const uint32_t pl = s_pl[j];
           if (pl >= 16u) v = parity_window_bf<true>(a.parity + s_po[j], pl, t);
         }
-        lds_put16<ACC>(s_acc + j * kSlot, t, v);
+        lds_put16(s_acc + j * kSlot, t, v);
       }
       __syncthreads();
       // packet starts before each 64-window block
@@ -241,7 +240,7 @@ __global__ __launch_bounds__(kRcThreads) void ragged_chunk_kernel(RaggedArgs a, 
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          if (tt[u] != 0xFFFFFFFFu) lds_xor16<ACC>(s_acc, tt[u], shr_bytes_bf(v[u], sh[u]));
+          if (tt[u] != 0xFFFFFFFFu) lds_xor16(s_acc, tt[u], shr_bytes_bf(v[u], sh[u]));
       }
     } else {
       // the per-group body (exact outputs and error bits), one wave per group,
@@ -255,9 +254,9 @@ __global__ __launch_bounds__(kRcThreads) void ragged_chunk_kernel(RaggedArgs a, 
         if (g >= a.n_groups) continue;
         GroupPrefetch f;
         group_scalars<RECOVER>(a, g, f);
-        group_vectors<RECOVER, true>(a, g, lane, f);
+        group_vectors<RECOVER>(a, g, lane, f);
         wave_lds_order();
-        ragged_group<RECOVER, true, 2, ACC>(a, g, lane, f, par, head, meta);
+        ragged_group<RECOVER>(a, g, lane, f, par, head, meta);
         wave_lds_order();
       }
     }
@@ -278,11 +277,11 @@ __global__ __launch_bounds__(kRcThreads) void ragged_chunk_kernel(RaggedArgs a, 
         uint8_t* dst = a.out + s_do[j];
         const uint32_t* acc = s_acc + j * kSlot;
         if (16u * t + 16u <= pl) {
-          st16t<true>(dst + 16u * t, lds_get16<ACC>(acc, t));
+          st16t<true>(dst + 16u * t, lds_get16(acc, t));
         } else {
           const uint32_t o = pl - 16u * t;  // 1..15
-          st16t<true>(dst + pl - 16u, bytes16_at(lds_get16<ACC>(acc, t - 1u),
-                                                 lds_get16<ACC>(acc, t), o));
+          st16t<true>(dst + pl - 16u, bytes16_at(lds_get16(acc, t - 1u),
+                                                 lds_get16(acc, t), o));
         }
       }
     }
@@ -338,7 +337,6 @@ __global__ __launch_bounds__(kRcThreads) void ragged_chunk2_kernel(RaggedArgs a,
                                                                    uint32_t* psync, uint32_t* phost,
                                                                    uint64_t* tstamp = nullptr) {
   static_assert(GP % kRcGPS == 0 && GP <= kRcThreads, "chunk shape");
-  constexpr int ACC = 1;
   constexpr uint32_t kSlot = 4u * kParWin;
   __shared__ uint32_t s_acc[GP * kSlot];
   __shared__ u32x4 s_pk[kRcMaxPk];
@@ -445,7 +443,7 @@ __global__ __launch_bounds__(kRcThreads) void ragged_chunk2_kernel(RaggedArgs a,
         const uint32_t pl = T.pl[bf][j];
         if (pl >= 16u) v = parity_window_bf<true>(a.parity + T.pof[bf][j], pl, t);
       }
-      lds_put16<ACC>(s_acc + j * kSlot, t, v);
+      lds_put16(s_acc + j * kSlot, t, v);
     }
     __syncthreads();
   };
@@ -499,7 +497,7 @@ __global__ __launch_bounds__(kRcThreads) void ragged_chunk2_kernel(RaggedArgs a,
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          if (tt[u] != 0xFFFFFFFFu) lds_xor16<ACC>(s_acc, tt[u], shr_bytes_bf(v[u], sh[u]));
+          if (tt[u] != 0xFFFFFFFFu) lds_xor16(s_acc, tt[u], shr_bytes_bf(v[u], sh[u]));
       }
     } else {
       uint32_t* base = s_acc + wv * (kSlot + 2u * kParWin + 4u * 64u);
@@ -511,9 +509,9 @@ __global__ __launch_bounds__(kRcThreads) void ragged_chunk2_kernel(RaggedArgs a,
         if (g >= a.n_groups) continue;
         GroupPrefetch f;
         group_scalars<RECOVER>(a, g, f);
-        group_vectors<RECOVER, true>(a, g, lane, f);
+        group_vectors<RECOVER>(a, g, lane, f);
         wave_lds_order();
-        ragged_group<RECOVER, true, 2, ACC>(a, g, lane, f, par, head, meta);
+        ragged_group<RECOVER>(a, g, lane, f, par, head, meta);
         wave_lds_order();
       }
     }
@@ -533,11 +531,11 @@ __global__ __launch_bounds__(kRcThreads) void ragged_chunk2_kernel(RaggedArgs a,
         uint8_t* dst = a.out + T.dof[bf][j];
         const uint32_t* acc = s_acc + j * kSlot;
         if (16u * t + 16u <= pl) {
-          st16t<true>(dst + 16u * t, lds_get16<ACC>(acc, t));
+          st16t<true>(dst + 16u * t, lds_get16(acc, t));
         } else {
           const uint32_t o = pl - 16u * t;
-          st16t<true>(dst + pl - 16u, bytes16_at(lds_get16<ACC>(acc, t - 1u),
-                                                 lds_get16<ACC>(acc, t), o));
+          st16t<true>(dst + pl - 16u, bytes16_at(lds_get16(acc, t - 1u),
+                                                 lds_get16(acc, t), o));
         }
       }
     }

@@ -84,7 +84,7 @@ struct V {
 
 template <bool REC, int DIAG = 0>
 static void blk(const RaggedArgs& a) {
-  hipLaunchKernelGGL((qfec::ragged_block_kernel<REC, 4, 8, 2, true, true, DIAG>),
+  hipLaunchKernelGGL((qfec::ragged_block_kernel<REC, 4, 8, DIAG>),
                      dim3((uint32_t)((a.n_groups + 7) / 8)), dim3(256), 0, 0, a);
 }
 

@@ -9,9 +9,10 @@
 //     palign 1: byte-packed.  slot: parity / revived row stride per group.
 //     mode 1: also the DIAG forms (whole-line stores; no stores; no tail);
 //     mode 2: the block kernel against ragged_multi_kernel (two groups per
-//     wave) on the given group shape (round 6's band table); mode 3: the
-//     payload loads / parity stores through the caches instead of nontemporal;
-//     mode 4: parity stores with explicit cache policies (sc1, sc0 sc1, nt sc1, ...).
+//     wave) on the given group shape (round 6's band table).
+//     (Modes 3 and 4, the cache-policy probe of round 6, and the U = 1 rows
+//     went with the kernel's switches: profiles/round6/tune_rblock_cache_r6p_*.txt,
+//     tune_rblock_pol_r6q.txt, profiles/round3/ragged_block/)
 //
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/tune/tune_rblock.hip \
 //          -o tools/tune/build/tune_rblock
@@ -61,10 +62,9 @@ struct V {
 // packet's partial last window by one lane after it -- measured exact and
 // 0.59-0.62 against the product's 0.69-0.71: profiles/round4/ragged_tl/,
 // commit ddd19fd; removed from the product)
-#define BLK(REC, U, TL)                                                                    \
+#define BLK(REC)                                                                           \
   [=](const RaggedArgs& a) {                                                               \
-    static_assert(!TL, "TL variant removed");                                              \
-    hipLaunchKernelGGL((qfec::ragged_block_kernel<REC, 4, 8, U, true, true, 0>),          \
+    hipLaunchKernelGGL((qfec::ragged_block_kernel<REC, 4, 8>),                             \
                        dim3((uint32_t)((a.n_groups + 7) / 8)), dim3(256), 0, 0, a);        \
   }
 // round 6: DIAG 1 (no stores), 2 (output rows stored as whole 128-B lines,
@@ -73,7 +73,7 @@ struct V {
 // 4 (no tail logic: every window XORed whole), 5 (4 without stores)
 #define BLKD(REC, D)                                                                       \
   [=](const RaggedArgs& a) {                                                               \
-    hipLaunchKernelGGL((qfec::ragged_block_kernel<REC, 4, 8, 2, true, true, D>),          \
+    hipLaunchKernelGGL((qfec::ragged_block_kernel<REC, 4, 8, D>),                          \
                        dim3((uint32_t)((a.n_groups + 7) / 8)), dim3(256), 0, 0, a);        \
   }
 
@@ -155,8 +155,8 @@ int main(int argc, char** argv) {
   r.out_off = d_poff;
   r.parity_len_out = nullptr;
   r.out = out_ref;
-  BLK(false, 2, false)(e);  // the product's outputs: the reference of every variant
-  BLK(true, 2, false)(r);
+  BLK(false)(e);  // the product's outputs: the reference of every variant
+  BLK(true)(r);
   CK(hipDeviceSynchronize());
   RaggedArgs ev = e, rv = r;  // variants write elsewhere
   ev.out = buf;
@@ -168,35 +168,17 @@ int main(int argc, char** argv) {
   if (mode == 2) {  // round 6 band table: the block kernel against two groups per wave
 #define MULTI(REC)                                                                          \
   [=](const RaggedArgs& a) {                                                                \
-    hipLaunchKernelGGL((qfec::ragged_multi_kernel<REC, true, 2, 2, 4>),                     \
+    hipLaunchKernelGGL((qfec::ragged_multi_kernel<REC>),                                    \
                        dim3((uint32_t)((a.n_groups + 7) / 8)), dim3(256), 0, 0, a);         \
   }
-    vs.push_back({"block encode", false, BLK(false, 2, false)});
+    vs.push_back({"block encode", false, BLK(false)});
     vs.push_back({"multi2 encode", false, MULTI(false)});
-    vs.push_back({"block recover", true, BLK(true, 2, false)});
+    vs.push_back({"block recover", true, BLK(true)});
     vs.push_back({"multi2 recover", true, MULTI(true)});
   } else {
-  vs.push_back({"product AL U2 encode", false, BLK(false, 2, false)});
-  vs.push_back({"product AL U1 encode", false, BLK(false, 1, false)});
-  vs.push_back({"product AL U2 encode (again)", false, BLK(false, 2, false)});
-  vs.push_back({"product AL U2 recover", true, BLK(true, 2, false)});
-  vs.push_back({"product AL U1 recover", true, BLK(true, 1, false)});
-  if (mode == 3) {  // round 6: cache policy of the payload loads / parity stores
-    vs.push_back({"cached stores encode", false, BLKD(false, 8)});
-    vs.push_back({"cached stores recover", true, BLKD(true, 8)});
-    vs.push_back({"cached loads encode", false, BLKD(false, 16)});
-    vs.push_back({"cached loads recover", true, BLKD(true, 16)});
-    vs.push_back({"cached both encode", false, BLKD(false, 24)});
-    vs.push_back({"cached both recover", true, BLKD(true, 24)});
-  }
-  if (mode == 4) {  // round 6: explicit store policies (st16pol)
-    vs.push_back({"stores sc1 encode", false, BLKD(false, 32)});
-    vs.push_back({"stores sc0 sc1 encode", false, BLKD(false, 64)});
-    vs.push_back({"stores nt sc1 encode", false, BLKD(false, 96)});
-    vs.push_back({"stores nt sc0 sc1 encode", false, BLKD(false, 128)});
-    vs.push_back({"stores sc1 recover", true, BLKD(true, 32)});
-    vs.push_back({"stores nt sc1 recover", true, BLKD(true, 96)});
-  }
+  vs.push_back({"product encode", false, BLK(false)});
+  vs.push_back({"product encode (again)", false, BLK(false)});
+  vs.push_back({"product recover", true, BLK(true)});
   const bool diag = mode == 1;
   if (diag) {
     vs.push_back({"whole-line stores encode", false, BLKD(false, 2)});

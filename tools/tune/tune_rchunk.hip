@@ -7,7 +7,6 @@
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/tune/tune_rchunk.hip -o tools/tune/build/tune_rchunk
 // run:   tune_rchunk [reps] [rounds]
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
-#include "ragged_legacy.inc"
 #include "ragged_chunk.inc"
 
 #include <algorithm>
@@ -47,7 +46,7 @@ using qfec::RaggedArgs;
 
 template <bool REC>
 static void launch_multi(const RaggedArgs& a, uint64_t G) {
-  hipLaunchKernelGGL((qfec::ragged_multi_kernel<REC, true, 2>), dim3((uint32_t)((G + 7) / 8)),
+  hipLaunchKernelGGL((qfec::ragged_multi_kernel<REC>), dim3((uint32_t)((G + 7) / 8)),
                      dim3(256), 0, 0, a);
 }
 

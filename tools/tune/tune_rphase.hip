@@ -492,7 +492,7 @@ static int g_ncu = 256;
 
 #define BLK(REC)                                                                           \
   [=](const RaggedArgs& a) {                                                               \
-    hipLaunchKernelGGL((qfec::ragged_block_kernel<REC, 4, 8, 2, true, true, 0>),          \
+    hipLaunchKernelGGL((qfec::ragged_block_kernel<REC, 4, 8>),          \
                        dim3((uint32_t)((a.n_groups + 7) / 8)), dim3(256), 0, 0, a);        \
   }
 

@@ -1204,7 +1204,7 @@ static uint64_t g_total_pk = 0;
 
 #define BLK(REC)                                                                           \
   [=](const RaggedArgs& a) {                                                               \
-    hipLaunchKernelGGL((qfec::ragged_block_kernel<REC, 4, 8, 2, true, true, 0>),          \
+    hipLaunchKernelGGL((qfec::ragged_block_kernel<REC, 4, 8>),          \
                        dim3((uint32_t)((a.n_groups + 7) / 8)), dim3(256), 0, 0, a);        \
   }
 

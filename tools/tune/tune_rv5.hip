@@ -134,10 +134,10 @@ __global__ __launch_bounds__(64 * WAVES) void rv5_kernel(RaggedArgs a, uint32_t*
       uint8_t* dst = a.out + s_sdoff[s];
       const uint32_t* ac = s_ring + s * kAccWords;
       if (16u * t + 16u <= plen) {
-        st16t<true>(dst + 16u * t, lds_get16<1>(ac, t));
+        st16t<true>(dst + 16u * t, lds_get16(ac, t));
       } else {
         const uint32_t o = plen - 16u * t;
-        st16t<true>(dst + plen - 16u, bytes16_at(lds_get16<1>(ac, t - 1u), lds_get16<1>(ac, t), o));
+        st16t<true>(dst + plen - 16u, bytes16_at(lds_get16(ac, t - 1u), lds_get16(ac, t), o));
       }
     }
     __syncthreads();
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(64 * WAVES) void rv5_kernel(RaggedArgs a, uint32_t*
         const uint32_t jq = q / (uint32_t)kParWin, t = q - jq * (uint32_t)kParWin;
         u32x4 w = {0u, 0u, 0u, 0u};
         if (jq < ng) w = parity_window_bf<true>(a.parity + s_poff[jq], s_pl[jq], t);
-        lds_put16<1>(acc + jq * kAccWords, t, w);
+        lds_put16(acc + jq * kAccWords, t, w);
       }
     }
     uint32_t len = 0, offlo = 0, offhi = 0, j = 0;
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(64 * WAVES) void rv5_kernel(RaggedArgs a, uint32_t*
     if (!RECOVER) {
       for (uint32_t q = tid; q < GPB * (uint32_t)kParWin; q += NT) {
         const uint32_t jq = q / (uint32_t)kParWin, t = q - jq * (uint32_t)kParWin;
-        lds_put16<1>(acc + jq * kAccWords, t, u32x4{0u, 0u, 0u, 0u});
+        lds_put16(acc + jq * kAccWords, t, u32x4{0u, 0u, 0u, 0u});
       }
     }
     __syncthreads();
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(64 * WAVES) void rv5_kernel(RaggedArgs a, uint32_t*
             const u32x4 mm = shr_bytes_bf(inp[u] ? ones : v[u], sh[u]);
             w = inp[u] ? (mm & v[u]) : mm;
           }
-          lds_xor16<1, __HIP_MEMORY_SCOPE_WORKGROUP>(acc, tt[u], w);
+          lds_xor16<__HIP_MEMORY_SCOPE_WORKGROUP>(acc, tt[u], w);
         }
     }
     __syncthreads();
@@ -321,10 +321,10 @@ __global__ __launch_bounds__(64 * WAVES) void rv5_kernel(RaggedArgs a, uint32_t*
         uint8_t* dst = a.out + s_doff[jq];
         const uint32_t* ac = acc + jq * kAccWords;
         if (16u * t + 16u <= plen) {
-          st16t<true>(dst + 16u * t, lds_get16<1>(ac, t));
+          st16t<true>(dst + 16u * t, lds_get16(ac, t));
         } else {
           const uint32_t o = plen - 16u * t;
-          st16t<true>(dst + plen - 16u, bytes16_at(lds_get16<1>(ac, t - 1u), lds_get16<1>(ac, t), o));
+          st16t<true>(dst + plen - 16u, bytes16_at(lds_get16(ac, t - 1u), lds_get16(ac, t), o));
         }
       }
       __syncthreads();
@@ -455,12 +455,12 @@ int main(int argc, char** argv) {
     return [=](const RaggedArgs& a) {
       const dim3 g((uint32_t)((a.n_groups + 7) / 8)), bl(256);
       if (rec) {
-        if (diag == 4) hipLaunchKernelGGL((qfec::ragged_block_kernel<true, 4, 8, 2, true, true, 4>), g, bl, 0, 0, a);
-        else hipLaunchKernelGGL((qfec::ragged_block_kernel<true, 4, 8, 2, true, true, 0>), g, bl, 0, 0, a);
+        if (diag == 4) hipLaunchKernelGGL((qfec::ragged_block_kernel<true, 4, 8, 4>), g, bl, 0, 0, a);
+        else hipLaunchKernelGGL((qfec::ragged_block_kernel<true, 4, 8, 0>), g, bl, 0, 0, a);
       } else {
-        if (diag == 4) hipLaunchKernelGGL((qfec::ragged_block_kernel<false, 4, 8, 2, true, true, 4>), g, bl, 0, 0, a);
-        else if (diag == 5) hipLaunchKernelGGL((qfec::ragged_block_kernel<false, 4, 8, 2, true, true, 5>), g, bl, 0, 0, a);
-        else hipLaunchKernelGGL((qfec::ragged_block_kernel<false, 4, 8, 2, true, true, 0>), g, bl, 0, 0, a);
+        if (diag == 4) hipLaunchKernelGGL((qfec::ragged_block_kernel<false, 4, 8, 4>), g, bl, 0, 0, a);
+        else if (diag == 5) hipLaunchKernelGGL((qfec::ragged_block_kernel<false, 4, 8, 5>), g, bl, 0, 0, a);
+        else hipLaunchKernelGGL((qfec::ragged_block_kernel<false, 4, 8, 0>), g, bl, 0, 0, a);
       }
     };
   };

@@ -53,9 +53,9 @@ __global__ __launch_bounds__(64) void svcgroup_probe(qfec::RaggedArgs a, const u
   a.parity_off = reinterpret_cast<const uint64_t*>(tb + kTPoff);
   uint64_t t[8];
   t[0] = wall_clock64();
-  qfec::window_group<false, true, qfec::kSvcPB>(a, 0, lane, s_par, s_head, s_meta);
+  qfec::window_group<false, qfec::kSvcPB>(a, 0, lane, s_par, s_head, s_meta);
   t[1] = wall_clock64();
-  qfec::window_group<false, true, qfec::kSvcPB>(a, 0, lane, s_par, s_head, s_meta);
+  qfec::window_group<false, qfec::kSvcPB>(a, 0, lane, s_par, s_head, s_meta);
   t[2] = wall_clock64();
   __threadfence_system();
   t[3] = wall_clock64();
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(64) void svcgroup_probe(qfec::RaggedArgs a, const u
   }
   asm volatile("" ::"v"((uint32_t)x));
   t[4] = wall_clock64();
-  qfec::window_group<false, true, qfec::kSvcPB>(a, 0, lane, s_par, s_head, s_meta);
+  qfec::window_group<false, qfec::kSvcPB>(a, 0, lane, s_par, s_head, s_meta);
   t[5] = wall_clock64();
   __threadfence_system();
   t[6] = wall_clock64();
