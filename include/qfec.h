@@ -27,6 +27,11 @@
  *       keep that receive map (the group's received_packets_) on the device:
  *       Update()'s duplicate check and the drop of a packet that failed to
  *       decrypt, before the fold; the close then reads the map by slot.
+ *   qfec_bin_arrivals
+ *       is QuicConnection::GetFecGroup handing each arriving packet to its
+ *       group (the receive path at quic_connection.cc:1388-1392), for a whole
+ *       turn: per-packet records in arrival order become the per-slot CSR
+ *       tables the admit reads.
  *   qfec_recover_batch / _strided / qfec_recover_ragged
  *       replaces QuicFecGroup::UpdateFec + Update(received) + CanRevive() +
  *       Revive().  Receive-side hook: QuicConnection::ProcessValidatedPacket
@@ -605,6 +610,70 @@ int qfec_revive_tracked(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride, 
                         const uint64_t* out_off, uint16_t* out_len, uint8_t* status,
                         uint8_t* revived_idx, uint64_t* revived_list, uint64_t* counts,
                         uint32_t release_mask, uint32_t flags);
+
+/* The turn's CSR tables built on the device: QuicConnection::GetFecGroup
+ * handing each arriving packet to its group (the receive path at
+ * quic_connection.cc:1388-1392), for a whole turn at once.  Sockets deliver
+ * packets in arrival order, interleaved across connections and groups;
+ * qfec_admit_ragged wants them listed per group.  What the host knows per
+ * packet without grouping anything -- the slot its group holds, its position
+ * in the group, where its plaintext will lie and how long it is -- goes to the
+ * device as flat records in arrival order, and this call bins them by slot: a
+ * stable counting sort.  The turn is open (in arrival order) ->
+ * qfec_bin_arrivals -> qfec_admit_ragged -> qfec_accumulate_ragged ->
+ * qfec_revive_tracked on one stream, with no sync and no host decision in
+ * between.  The host still assigns slots and positions.
+ *
+ * Inputs, n_packets records in arrival order: pkt_slot[p] the slot of the
+ * packet's group, or QFEC_NO_SLOT for a packet that is no candidate
+ * (unprotected, or its group already evicted); pkt_off, pkt_len, pkt_idx and
+ * pkt_ok per packet as qfec_admit_ragged defines them.  pkt_ok may be NULL:
+ * pkt_ok_out is then not written and may be NULL.  The call never dereferences
+ * pkt_off and never reads a payload byte; offsets, lengths and indices are
+ * carried, not judged (the admit judges them).
+ * Outputs, in lockstep with the slots -- group s is slot s, so the tables feed
+ * qfec_admit_ragged and qfec_accumulate_ragged with slot == NULL and n_groups
+ * == n_slots: grp_ptr_out[0] = 0 and grp_ptr_out[s+1] - grp_ptr_out[s] = the
+ * packets with pkt_slot == s (a slot nobody names gets an empty group, which
+ * both calls define as a no-op -- but the admit judges the slot of every group,
+ * an empty one's too, so a slot no group holds keeps a legal slot_k and
+ * acc_len); at grp_ptr_out[s] + r lies the r-th packet of
+ * slot s in ARRIVAL order (ascending p): its pkt_off, pkt_len, pkt_idx, its
+ * pkt_ok if given, and in src_out (may be NULL) its arrival index p, which
+ * maps the admit's verdict[q] back to a packet.  Entries from
+ * grp_ptr_out[n_slots] on are not written; the caller guarantees room for
+ * n_packets entries in each output table and n_slots + 1 in grp_ptr_out.
+ * The outputs are a pure function of the inputs, with one exception: a slot
+ * named by more than 255 packets in the call.  Its entries are exactly its
+ * packets, each once, the five tables consistent per entry, in unspecified
+ * order; the admit refuses such a group (k_g > 255) and latches, so this call
+ * does not, and it spends no more than linear time on it.
+ * counts[0..2] (may be NULL): packets binned, packets with QFEC_NO_SLOT (a
+ * result), packets with any other pkt_slot >= n_slots.  The last are skipped
+ * and latched on the device like qfec_accumulate_ragged's slot >= n_slots, and
+ * returned by the next qfec_sync as -QUIC_INVALID_FEC_DATA; every other
+ * packet's outputs are right.
+ * Refused on the host (nothing launched, nothing written): QFEC_PTR_HOST,
+ * QFEC_PTR_MAPPED or QFEC_ASYNC; a NULL buffer other than pkt_ok, pkt_ok_out
+ * without pkt_ok, src_out and counts; pkt_ok given without pkt_ok_out;
+ * n_packets >= 2^32 or n_slots >= 2^32 (QFEC_ERR_INTERNAL).  n_slots == 0
+ * succeeds before the buffers are looked at (counts, if given, receives three
+ * zeroes; nothing else is written).  n_packets == 0 with n_slots > 0 is an
+ * ordinary call: grp_ptr_out is required and receives n_slots + 1 zeroes,
+ * counts three, and no other table is looked at.
+ * QFEC_CACHED and QFEC_SMALL_GROUPS are accepted and change nothing.  Device
+ * pointers only; the call only queues work on the context's stream, never
+ * waits and never reads anything back.  Its intermediate state lives in the
+ * context-owned scratch of qfec_revive_batch: 20 bytes per packet (a 16-byte
+ * record and a provisional rank), 4 bytes per slot (a counter), 4 bytes per
+ * 256 slots and 48 bytes.  An admit that follows on the same stream reuses
+ * the block; stream order makes that safe, as between admit and revive. */
+#define QFEC_NO_SLOT 0xFFFFFFFFu /* pkt_slot value: this packet is in no open group */
+int qfec_bin_arrivals(qfec_ctx* ctx, const uint32_t* pkt_slot, const uint64_t* pkt_off,
+                      const uint16_t* pkt_len, const uint8_t* pkt_idx, const uint8_t* pkt_ok,
+                      uint64_t n_packets, uint64_t n_slots, uint32_t* grp_ptr_out,
+                      uint64_t* pkt_off_out, uint16_t* pkt_len_out, uint8_t* pkt_idx_out,
+                      uint8_t* pkt_ok_out, uint32_t* src_out, uint64_t* counts, uint32_t flags);
 
 /* ---- single buffer ------------------------------------------------------ */
 /* out[j] ^= in[j] for j < n (QuicFecGroupInterface::XorBuffers). */

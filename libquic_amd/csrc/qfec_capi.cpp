@@ -1431,8 +1431,7 @@ namespace {
 // their launches: grown to revive_scratch_bytes(n_groups) -- the outgrown block
 // is retired, not freed: hipFree would wait for the device -- and ordered after
 // the last revive call's kernels if that call ran on another stream.
-int revive_scratch_acquire(qfec_ctx* ctx, uint64_t n_groups) {
-  const uint64_t need = qfec::revive_scratch_bytes(n_groups);
+int revive_scratch_acquire_bytes(qfec_ctx* ctx, uint64_t need) {
   if (ctx->revive_bytes < need) {
     const size_t want = std::max<size_t>({(size_t)need, 2 * ctx->revive_bytes, 4096});
     void* grown = nullptr;
@@ -1446,6 +1445,10 @@ int revive_scratch_acquire(qfec_ctx* ctx, uint64_t n_groups) {
   if (ctx->revive_recorded && ctx->revive_stream != ctx->stream)
     QFEC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->revive_done, 0));
   return QFEC_OK;
+}
+
+int revive_scratch_acquire(qfec_ctx* ctx, uint64_t n_groups) {
+  return revive_scratch_acquire_bytes(ctx, qfec::revive_scratch_bytes(n_groups));
 }
 
 // After a revive call's launches: the event a call on another stream waits for.
@@ -2346,6 +2349,59 @@ int qfec_admit_ragged(qfec_ctx* ctx, const uint64_t* pkt_off, const uint16_t* pk
   a.lim = row_limit(acc_stride);
   qfec::admit_scratch_layout(a, ctx->d_revive);
   QFEC_HIP(ctx, qfec::launch_admit_ragged(a, ctx->stream));
+  return revive_scratch_release(ctx);
+}
+
+// QuicConnection::GetFecGroup handing each arriving packet to its group
+// (quic_connection.cc:1388-1392 is where the receive path met the FEC group),
+// for a whole turn: the arrival-order records binned by slot into the CSR
+// tables the admit reads.  One memset and six kernels on the stream, in the
+// revive calls' scratch; every check that needs the tables is the kernels'.
+int qfec_bin_arrivals(qfec_ctx* ctx, const uint32_t* pkt_slot, const uint64_t* pkt_off,
+                      const uint16_t* pkt_len, const uint8_t* pkt_idx, const uint8_t* pkt_ok,
+                      uint64_t n_packets, uint64_t n_slots, uint32_t* grp_ptr_out,
+                      uint64_t* pkt_off_out, uint16_t* pkt_len_out, uint8_t* pkt_idx_out,
+                      uint8_t* pkt_ok_out, uint32_t* src_out, uint64_t* counts, uint32_t flags) {
+  const char* const what = "bin arrivals";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_device_only(ctx, what, flags))) return rc;
+  if (n_slots == 0) return zero_counts(ctx, counts, 3);
+  if (!grp_ptr_out ||
+      (n_packets != 0 && (!pkt_slot || !pkt_off || !pkt_len || !pkt_idx || !pkt_off_out ||
+                          !pkt_len_out || !pkt_idx_out)))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: null buffer (only pkt_ok, pkt_ok_out without pkt_ok, src_out and counts "
+                "may be NULL)", what);
+  if (n_packets != 0 && pkt_ok && !pkt_ok_out)
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: pkt_ok given without pkt_ok_out", what);
+  if (n_packets >= (1ull << 32) || n_slots >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: 2^32 or more packets or slots (packet and slot indices are 32 bits)", what);
+  if (n_packets == 0) {  // every slot's group is empty
+    QFEC_HIP(ctx, hipMemsetAsync(grp_ptr_out, 0, (n_slots + 1) * sizeof(uint32_t), ctx->stream));
+    return zero_counts(ctx, counts, 3);
+  }
+  if ((rc = revive_scratch_acquire_bytes(ctx, qfec::bin_scratch_bytes(n_packets, n_slots))))
+    return rc;
+  qfec::BinArgs a{};
+  a.pkt_slot = pkt_slot;
+  a.pkt_off = pkt_off;
+  a.pkt_len = pkt_len;
+  a.pkt_idx = pkt_idx;
+  a.pkt_ok = pkt_ok;
+  a.n_packets = n_packets;
+  a.n_slots = (uint32_t)n_slots;
+  a.grp_ptr_out = grp_ptr_out;
+  a.pkt_off_out = pkt_off_out;
+  a.pkt_len_out = pkt_len_out;
+  a.pkt_idx_out = pkt_idx_out;
+  a.pkt_ok_out = pkt_ok_out;
+  a.src_out = src_out;
+  a.counts = counts;
+  a.err = ctx->d_err;
+  a.ncu = ctx->ncu;
+  qfec::bin_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_bin_arrivals(a, ctx->stream));
   return revive_scratch_release(ctx);
 }
 

@@ -308,6 +308,54 @@ static_assert(kReviveTile * 4 >= 16 && kReviveListPad * 8 >= 16,
 // n_groups > 0.
 hipError_t launch_admit_ragged(const AdmitArgs& a, hipStream_t s);
 
+// qfec_bin_arrivals: a turn's per-packet records in arrival order to the
+// per-slot CSR tables the admit reads (layout and rule as include/qfec.h).
+// Scratch, a block of bin_scratch_bytes(n_packets, n_slots) in the revive
+// calls' allocation: the three tallies (binned, no slot, out of range) and a
+// counter per slot, zeroed together in front of the kernels; a 16-byte record
+// and a provisional rank per packet; a word per tile of kReviveTile slots.
+constexpr uint32_t kBinNoSlot = 0xFFFFFFFFu;  // QFEC_NO_SLOT
+struct BinArgs {
+  const uint32_t* pkt_slot;
+  const uint64_t* pkt_off;  // carried, never dereferenced
+  const uint16_t* pkt_len;
+  const uint8_t* pkt_idx;
+  const uint8_t* pkt_ok;  // nullable: pkt_ok_out is not written
+  uint64_t n_packets;     // 0 < n_packets < 2^32
+  uint32_t n_slots;       // > 0
+  uint32_t* grp_ptr_out;
+  uint64_t* pkt_off_out;
+  uint16_t* pkt_len_out;
+  uint8_t* pkt_idx_out;
+  uint8_t* pkt_ok_out;
+  uint32_t* src_out;  // nullable
+  uint64_t* counts;   // nullable: [binned, no slot, out of range]
+  unsigned long long* tally;  // scratch: 3 (+ 1 of padding)
+  uint32_t* cnt;              // scratch: n_slots
+  uint4* rec;                 // scratch: n_packets, 16-byte aligned
+  uint32_t* rank;             // scratch: n_packets
+  uint32_t* tile_off;         // scratch: 1 per tile of slots
+  uint32_t* err;
+  uint32_t ncu;
+};
+// the tallies and the counters: what the memset in front of the kernels clears
+inline uint64_t bin_scratch_zeroed(uint64_t n_slots) { return 32 + n_slots * 4; }
+inline uint64_t bin_scratch_bytes(uint64_t n_packets, uint64_t n_slots) {
+  return ((bin_scratch_zeroed(n_slots) + 15) & ~15ull) + n_packets * 20 +
+         revive_tiles(n_slots) * 4;
+}
+inline void bin_scratch_layout(BinArgs& a, void* block) {
+  uint8_t* p = static_cast<uint8_t*>(block);
+  a.tally = reinterpret_cast<unsigned long long*>(p);
+  a.cnt = reinterpret_cast<uint32_t*>(p + 32);
+  a.rec = reinterpret_cast<uint4*>(p + ((bin_scratch_zeroed(a.n_slots) + 15) & ~15ull));
+  a.rank = reinterpret_cast<uint32_t*>(a.rec + a.n_packets);
+  a.tile_off = a.rank + a.n_packets;
+}
+// One memset and six launches on s (count, tile, scan, ptr, scatter, order),
+// ordered by the stream alone.  n_packets > 0, n_slots > 0.
+hipError_t launch_bin_arrivals(const BinArgs& a, hipStream_t s);
+
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch
 // per batch (the launch is most of a small flush's connection-thread cost).

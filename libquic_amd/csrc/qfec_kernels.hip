@@ -1185,6 +1185,216 @@ __global__ __launch_bounds__(kReviveTile) void admit_scatter_kernel(AdmitArgs a)
 }
 static_assert(kReviveTile == 256, "four waves' counts are summed by hand above");
 
+// ---------------------------------------------------------------------------
+// Arrival order to per-slot CSR tables (qfec_bin_arrivals): a stable counting
+// sort keyed by slot, in front of the admit.
+// ---------------------------------------------------------------------------
+// Six kernels on the stream behind one memset of the tallies and the per-slot
+// counters; none reads a payload byte or dereferences pkt_off:
+//   count   : one lane per packet classifies its slot (none, out of range,
+//             binned) and takes a provisional rank from an atomic on the slot's
+//             counter, one atomic per run of neighbouring lanes with one
+//             slot; the three tallies per wave by ballot, per workgroup
+//             through LDS, one atomic per workgroup and class;
+//   tile    : the sum of every tile of kReviveTile slot counters;
+//   scan    : one workgroup, an exclusive scan over the tile sums in place,
+//             grp_ptr_out[n_slots] and counts;
+//   ptr     : a scan of the tile's 256 counters gives grp_ptr_out[s];
+//   scatter : one lane per packet, ONE aligned 16-B record (off, len | idx <<
+//             16 | ok << 24, p) to scratch at grp_ptr_out[s] + provisional rank;
+//   order   : a workgroup per tile of slots owns one contiguous run of
+//             records: one lane per RECORD finds its slot by bisection over the
+//             tile's 257 pointers in LDS, its final rank as the number of
+//             records of the slot with a smaller p (segments of at most 255;
+//             longer ones stay as they lie: nothing here grows faster than the
+//             segment), and writes the five tables.
+// The atomics decide only the provisional place inside a segment; the order
+// pass removes that freedom.  Every index formed from pkt_slot is checked
+// against n_slots first, and every place against n_packets.
+__global__ __launch_bounds__(kReviveTile) void bin_count_kernel(BinArgs a) {
+  __shared__ uint32_t s_w[kReviveTile / 64][3];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t n_bin = 0, n_none = 0, n_bad = 0;  // the wave's (uniform)
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const uint32_t s = a.pkt_slot[in ? p : a.n_packets - 1u];  // (clamped, not masked)
+    const bool binned = in && s < a.n_slots;
+    const bool none = in && s == kBinNoSlot;
+    const bool bad = in && !binned && !none;
+    // One atomic per RUN of neighbouring lanes with one slot (a burst of one
+    // group's packets), taken by the run's first lane for all of it: arrivals
+    // already grouped cost a tenth of the atomics, a random order what it did.
+    // (a binned lane's slot differs from any lane's that is not binned)
+    const uint32_t prev = __shfl_up(s, 1);
+    const bool head = binned && (lane == 0u || prev != s);
+    const uint64_t heads = __ballot(head), enders = heads | ~__ballot(binned);
+    // the lanes at or below this one, as 32-bit words (32-bit shifts only)
+    const uint32_t m_lo = lane < 32u ? (2u << lane) - 1u : 0xFFFFFFFFu;
+    const uint32_t m_hi = lane < 32u ? 0u : (2u << (lane - 32u)) - 1u;
+    const uint32_t h_lo = (uint32_t)heads & m_lo, h_hi = (uint32_t)(heads >> 32) & m_hi;
+    const uint32_t e_lo = (uint32_t)enders & ~m_lo, e_hi = (uint32_t)(enders >> 32) & ~m_hi;
+    // its run: from the last head at or below it to the next head or unbinned lane
+    const uint32_t first = h_hi ? 63u - (uint32_t)__builtin_clz(h_hi)
+                                : (h_lo ? 31u - (uint32_t)__builtin_clz(h_lo) : 0u);
+    const uint32_t end = e_lo ? (uint32_t)__builtin_ctz(e_lo)
+                              : (e_hi ? 32u + (uint32_t)__builtin_ctz(e_hi) : 64u);
+    uint32_t base = 0;
+    if (head) base = atomicAdd(&a.cnt[s], end - lane);
+    base = __shfl(base, first);
+    if (binned) a.rank[p] = base + (lane - first);
+    n_bin += (uint32_t)__popcll(__ballot(binned));
+    n_none += (uint32_t)__popcll(__ballot(none));
+    n_bad += (uint32_t)__popcll(__ballot(bad));
+  }
+  if (lane == 0u) {
+    s_w[wave][0] = n_bin;
+    s_w[wave][1] = n_none;
+    s_w[wave][2] = n_bad;
+  }
+  __syncthreads();
+  if (tid < 3u) {
+    const uint32_t t = s_w[0][tid] + s_w[1][tid] + s_w[2][tid] + s_w[3][tid];
+    if (t != 0u) atomicAdd(&a.tally[tid], (unsigned long long)t);
+    if (tid == 2u && t != 0u) atomicOr(a.err, kErrMissingIndex);
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void bin_tile_kernel(BinArgs a) {
+  __shared__ uint32_t s_w[kReviveTile / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const uint64_t s = tile * kReviveTile + tid;
+    const uint32_t c = wave_sum(s < a.n_slots ? a.cnt[s] : 0u);
+    if (lane == 0u) s_w[wave] = c;
+    __syncthreads();
+    if (tid == 0u) a.tile_off[tile] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    __syncthreads();  // s_w is reused by the next tile
+  }
+}
+
+// One workgroup: tile_off[i] = packets binned to the tiles before i (in place
+// over the tile sums: every lane reads its own word before it writes it), then
+// the totals.  All sums fit 32 bits: n_packets < 2^32.
+__global__ __launch_bounds__(kRvScanBlock) void bin_scan_kernel(BinArgs a) {
+  __shared__ uint32_t s_sum[kRvScanBlock / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
+  uint32_t base = 0;
+  for (uint64_t t0 = 0; t0 < ntile; t0 += kRvScanBlock) {
+    const uint64_t i = t0 + tid;
+    const uint32_t c = i < ntile ? a.tile_off[i] : 0u;
+    uint32_t x = c;  // inclusive scan within the wave
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63u) s_sum[wave] = x;
+    __syncthreads();
+    uint32_t before = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kRvScanBlock / 64; ++w) {
+      if (w < wave) before += s_sum[w];
+      tot += s_sum[w];
+    }
+    if (i < ntile) a.tile_off[i] = base + before + (x - c);
+    base += tot;
+    __syncthreads();
+  }
+  if (tid == 0u) {
+    a.grp_ptr_out[a.n_slots] = base;
+    if (a.counts) {
+      a.counts[0] = a.tally[0];
+      a.counts[1] = a.tally[1];
+      a.counts[2] = a.tally[2];
+    }
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void bin_ptr_kernel(BinArgs a) {
+  __shared__ uint32_t s_w[kReviveTile / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const uint64_t s = tile * kReviveTile + tid;
+    const uint32_t c = s < a.n_slots ? a.cnt[s] : 0u;
+    uint32_t x = c;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63u) s_w[wave] = x;
+    __syncthreads();
+    uint32_t pos = a.tile_off[tile] + (x - c);
+    for (uint32_t w = 0; w < wave; ++w) pos += s_w[w];
+    if (s < a.n_slots) a.grp_ptr_out[s] = pos;
+    __syncthreads();  // s_w is reused by the next tile
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void bin_scatter_kernel(BinArgs a) {
+  const uint32_t tid = threadIdx.x;
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const uint64_t pc = in ? p : a.n_packets - 1u;  // (clamped, not masked)
+    const uint32_t s = a.pkt_slot[pc];
+    const uint64_t off = a.pkt_off[pc];
+    const uint32_t len = a.pkt_len[pc], idx = a.pkt_idx[pc];
+    const uint32_t okp = a.pkt_ok ? (uint32_t)a.pkt_ok[pc] : 0u;
+    if (in && s < a.n_slots) {
+      const uint64_t pos = (uint64_t)a.grp_ptr_out[s] + a.rank[p];
+      if (pos < a.n_packets)
+        a.rec[pos] = make_uint4((uint32_t)off, (uint32_t)(off >> 32), len | (idx << 16) | (okp << 24),
+                                (uint32_t)p);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void bin_order_kernel(BinArgs a) {
+  __shared__ uint32_t s_ptr[kReviveTile + 1];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    // (slots past n_slots: empty segments at the run's end)
+    s_ptr[tid] = a.grp_ptr_out[min(tile * kReviveTile + tid, (uint64_t)a.n_slots)];
+    if (tid == 0u)
+      s_ptr[kReviveTile] = a.grp_ptr_out[min((tile + 1) * kReviveTile, (uint64_t)a.n_slots)];
+    __syncthreads();
+    const uint32_t first = s_ptr[0];
+    const uint32_t end = min(s_ptr[kReviveTile], (uint32_t)a.n_packets);
+    for (uint64_t q = (uint64_t)first + tid; q < end; q += kReviveTile) {
+      uint32_t lo = 0, hi = kReviveTile;  // s_ptr[lo] <= q < s_ptr[hi]
+#pragma unroll
+      for (uint32_t i = 0; i < 8u; ++i) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s_ptr[mid] <= (uint32_t)q) lo = mid;
+        else hi = mid;
+      }
+      const uint32_t seg = s_ptr[lo], k = s_ptr[lo + 1u] - seg;
+      const uint4 r = a.rec[q];
+      uint32_t place = (uint32_t)q;
+      if (k <= 255u) {
+        uint32_t before = 0;
+        for (uint32_t j = 0; j < k; ++j) before += a.rec[seg + j].w < r.w ? 1u : 0u;
+        place = seg + before;
+      }
+      a.pkt_off_out[place] = (uint64_t)r.x | ((uint64_t)r.y << 32);
+      a.pkt_len_out[place] = (uint16_t)r.z;
+      a.pkt_idx_out[place] = (uint8_t)(r.z >> 16);
+      if (a.pkt_ok) a.pkt_ok_out[place] = (uint8_t)(r.z >> 24);
+      if (a.src_out) a.src_out[place] = r.w;
+    }
+    __syncthreads();  // s_ptr is reused by the next tile
+  }
+}
+static_assert(kReviveTile == 256, "eight bisection steps; four waves' counts summed by hand");
+
 // The recover body over the work list, L >= 16: lanes, windows and loads as
 // fixed_xor_kernel; workgroup step i takes entries [i * gpb, (i + 1) * gpb).
 // `work` and `totals` are separate restrict parameters so that their loads
@@ -3610,6 +3820,29 @@ hipError_t launch_admit_ragged(const AdmitArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(admit_scan_kernel, dim3(1), dim3(kRvScanBlock), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(admit_scatter_kernel, dim3(grid), dim3(kReviveTile), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_bin_arrivals(const BinArgs& a, hipStream_t s) {
+  if (a.n_packets == 0 || a.n_slots == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(a.tally, 0, bin_scratch_zeroed(a.n_slots), s);
+  if (e != hipSuccess) return e;
+  // per packet: the workgroups loop, sixteen per CU, so that the tallies cost
+  // three atomics per workgroup and not per 256 packets
+  const uint32_t pgrid = (uint32_t)std::min<uint64_t>(
+      (a.n_packets + kReviveTile - 1) / kReviveTile, (uint64_t)(a.ncu ? a.ncu : 256u) * 16u);
+  const uint32_t sgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_slots), kMaxBlocks256);
+  hipLaunchKernelGGL(bin_count_kernel, dim3(pgrid), dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(bin_tile_kernel, dim3(sgrid), dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(kRvScanBlock), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(bin_ptr_kernel, dim3(sgrid), dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(bin_scatter_kernel, dim3(pgrid), dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(bin_order_kernel, dim3(sgrid), dim3(kReviveTile), 0, s, a);
   return hipGetLastError();
 }
 

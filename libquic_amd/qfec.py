@@ -37,6 +37,7 @@ QFEC_PKT_ADMITTED = 0
 QFEC_PKT_FAILED = 1
 QFEC_PKT_DUPLICATE = 2
 QFEC_PKT_INVALID = 3
+QFEC_NO_SLOT = 0xFFFFFFFF
 MAX_PACKET_SIZE = 1452
 DEFAULT_MAX_PACKET_SIZE = 1350
 MAX_GROUP_PACKETS = 255
@@ -99,6 +100,9 @@ SIGNATURES = [
     ("qfec_revive_tracked", C.c_int,
      [_vp, _u8p, C.c_uint64, _vp, _u8p, C.c_uint64, _u8p, _vp, C.c_uint64, C.c_uint64, _u8p, _vp,
       _vp, _u8p, _u8p, _vp, _vp, C.c_uint32, C.c_uint32]),
+    ("qfec_bin_arrivals", C.c_int,
+     [_vp, _vp, _vp, _vp, _u8p, _u8p, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _u8p, _u8p, _vp, _vp,
+      C.c_uint32]),
     ("qfec_xor_into", C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint32]),
     ("qfec_wire_write_private_header", C.c_size_t, [_vp, _u8p, C.c_size_t]),
     ("qfec_wire_parse_private_header", C.c_size_t,
@@ -561,6 +565,27 @@ class Context:
                                           n_groups, _ptr(out), _ptr(out_off), _ptr(out_len),
                                           _ptr(status), _ptr(revived_idx), _ptr(revived_list),
                                           _ptr(counts), release_mask, flags)
+        return self._check(rc)
+
+    def bin_arrivals(self, pkt_slot, pkt_off, pkt_len, pkt_idx, pkt_ok, n_packets, n_slots,
+                     grp_ptr_out, pkt_off_out, pkt_len_out, pkt_idx_out, *, pkt_ok_out=None,
+                     src_out=None, counts=None, flags=0):
+        """qfec_bin_arrivals: a turn's per-packet records in arrival order
+        (pkt_slot uint32 the slot of the packet's group or QFEC_NO_SLOT,
+        pkt_off uint64, pkt_len uint16, pkt_idx uint8, pkt_ok uint8 or None)
+        binned by slot into the lockstep CSR tables admit_ragged reads with
+        slot=None and n_groups = n_slots: grp_ptr_out (uint32[n_slots + 1]),
+        pkt_off_out, pkt_len_out, pkt_idx_out, pkt_ok_out (with pkt_ok) and
+        src_out (uint32, optional: the arrival index of every entry), each
+        with room for n_packets entries, stable within a slot.  counts
+        (uint64[3], optional): binned, QFEC_NO_SLOT, slot out of range (the
+        last latched).  Device pointers only; queued on the context's stream
+        (sync() before reading the results)."""
+        rc = self.lib.qfec_bin_arrivals(self.ctx, _ptr(pkt_slot), _ptr(pkt_off), _ptr(pkt_len),
+                                        _ptr(pkt_idx), _ptr(pkt_ok), n_packets, n_slots,
+                                        _ptr(grp_ptr_out), _ptr(pkt_off_out), _ptr(pkt_len_out),
+                                        _ptr(pkt_idx_out), _ptr(pkt_ok_out), _ptr(src_out),
+                                        _ptr(counts), flags)
         return self._check(rc)
 
     def xor_into(self, src, n, dst, *, host=False, mapped=False):
