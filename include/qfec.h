@@ -32,6 +32,11 @@
  *       group (the receive path at quic_connection.cc:1388-1392), for a whole
  *       turn: per-packet records in arrival order become the per-slot CSR
  *       tables the admit reads.
+ *   qfec_assign_slots
+ *       is the lookup inside that same GetFecGroup: group_map_ searched for
+ *       the packet's group and a new group inserted when there is none
+ *       (quic_connection.cc:1388-1392), for a whole turn: per-packet 64-bit
+ *       group keys become the per-packet slots the bin reads.
  *   qfec_recover_batch / _strided / qfec_recover_ragged
  *       replaces QuicFecGroup::UpdateFec + Update(received) + CanRevive() +
  *       Revive().  Receive-side hook: QuicConnection::ProcessValidatedPacket
@@ -519,8 +524,9 @@ int qfec_revive_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stri
  * a packet number already in received_packets_; folded twice it cancels out of
  * the row).  A receiver's turn is open -> qfec_admit_ragged ->
  * qfec_accumulate_ragged -> qfec_revive_tracked on one stream, with no sync
- * and no host decision in between.  The host still assigns slots and
- * positions (the private flags and the FEC group offset are cleartext).
+ * and no host decision in between.  The position is the cleartext FEC group
+ * offset byte; the slot is the host's lookup, or qfec_assign_slots' (below),
+ * which also lists what then remains with the host.
  *
  * qfec_admit_ragged never reads a payload byte.  pkt_off, pkt_len and grp_ptr
  * list the turn's CANDIDATES per group as qfec_accumulate_ragged's tables do;
@@ -622,7 +628,8 @@ int qfec_revive_tracked(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride, 
  * stable counting sort.  The turn is open (in arrival order) ->
  * qfec_bin_arrivals -> qfec_admit_ragged -> qfec_accumulate_ragged ->
  * qfec_revive_tracked on one stream, with no sync and no host decision in
- * between.  The host still assigns slots and positions.
+ * between.  The slots come from the host or from qfec_assign_slots (below);
+ * the position is the cleartext FEC group offset byte.
  *
  * Inputs, n_packets records in arrival order: pkt_slot[p] the slot of the
  * packet's group, or QFEC_NO_SLOT for a packet that is no candidate
@@ -674,6 +681,81 @@ int qfec_bin_arrivals(qfec_ctx* ctx, const uint32_t* pkt_slot, const uint64_t* p
                       uint64_t n_packets, uint64_t n_slots, uint32_t* grp_ptr_out,
                       uint64_t* pkt_off_out, uint16_t* pkt_len_out, uint8_t* pkt_idx_out,
                       uint8_t* pkt_ok_out, uint32_t* src_out, uint64_t* counts, uint32_t flags);
+
+/* Slots found or opened on the device: the group_map_ lookup and insert of
+ * QuicConnection::GetFecGroup (quic_connection.cc:1388-1392), for a whole turn
+ * at once.  The host appends one 64-bit group key per packet, built from what
+ * the cleartext header gives it (suggested: connection index << 40 | group
+ * number, the group number being the packet number minus the FEC group offset
+ * byte); this call resolves every key to the slot of its open group, or opens
+ * a group in a free slot, and writes the pkt_slot array qfec_bin_arrivals
+ * reads.  The turn is open -> qfec_assign_slots -> qfec_bin_arrivals ->
+ * qfec_admit_ragged -> qfec_accumulate_ragged -> qfec_revive_tracked on one
+ * stream, with no sync and no host decision in between.  No state is added:
+ * which slots are open is acc_len[s] > 0, and by the fresh-slot rule of the
+ * accumulate, the admit and the tracked revive a slot of length 0 is FREE
+ * whatever slot_key[s] holds.  A slot released by any close call is free for
+ * the next assign with nothing cleared: no free list, no tombstone.
+ *
+ * Inputs, n_packets records in arrival order: pkt_key[p] an opaque 64-bit name
+ * of the packet's group (never interpreted), or QFEC_NO_KEY for a packet in no
+ * FEC group; pkt_k[p] the group's K as the host knows it, read only for a
+ * packet that opens a group and carried, not judged (the admit judges K == 0
+ * and a map beyond map_stride).  Per slot: slot_key[s], the key the slot's
+ * group was opened under, read where acc_len[s] > 0 and written where the call
+ * opens a group; slot_k[s], the admit's table, written where the call opens a
+ * group; acc_len, read only.
+ * The rule, stated sequentially; the outputs are exactly these, a pure function
+ * of the inputs (no scheduling, atomic order or hash shows in them):
+ *   index maps each key to the LOWEST slot s with acc_len[s] > 0 and
+ *     slot_key[s] == key (two open slots under one key cannot arise from this
+ *     call's own outputs; if they do the lower wins and nothing is latched); an
+ *     open slot holding QFEC_NO_KEY, a group the host opened itself, matches no
+ *     packet;
+ *   free is the ascending list of the slots with acc_len[s] == 0;
+ *   packets are taken in ascending p:
+ *     pkt_key[p] == QFEC_NO_KEY: pkt_slot_out[p] = QFEC_NO_SLOT, counts[2]++;
+ *     the key is in index: pkt_slot_out[p] = that slot, counts[0]++;
+ *     the key was opened earlier in this call: that slot, counts[1]++;
+ *     otherwise, free not used up: s = the next entry of free, slot_key[s] =
+ *       key, slot_k[s] = pkt_k[p], pkt_slot_out[p] = s, counts[1]++ and
+ *       counts[3]++ (groups opened);
+ *     otherwise: pkt_slot_out[p] = QFEC_NO_SLOT, counts[4]++ -- turned away,
+ *       as the reference refuses a group beyond kMaxFecGroups: a result, not an
+ *       error (later packets of that key in the call are turned away too).
+ * Equivalently the r-th new key by FIRST arrival gets free[r] if r < |free|,
+ * else none, and its K from its first packet.  Nothing is latched.
+ * Never written: slot_key / slot_k of slots the call does not open; acc_len;
+ * anything past pkt_slot_out[n_packets - 1].
+ * A group opened here has length 0 until its first packet is folded, so each
+ * assign is followed on its stream by bin -> admit -> accumulate over the same
+ * acc_len before the next assign: until then the slot still counts as free.
+ * If every candidate of a new group fails its tag nothing was folded, and the
+ * slot is free again with nothing lost.
+ * What stays with the host: the key and the position (pkt_idx) from the
+ * cleartext header; the policy, expressed through QFEC_NO_KEY -- which packets
+ * are candidates at all, and a per-connection watermark below which a closed
+ * group is never reopened (a late duplicate of a released group would open it
+ * anew under its key); and forced closes, for which it reads slot_key back.
+ * Refused on the host (nothing launched, nothing written): QFEC_PTR_HOST,
+ * QFEC_PTR_MAPPED or QFEC_ASYNC; a NULL buffer other than counts; n_packets >=
+ * 2^32 or n_slots >= 2^32, or more than 2^30 of both together
+ * (QFEC_ERR_INTERNAL).  n_packets == 0 succeeds before the buffers are looked
+ * at (counts, if given, receives five zeroes).  n_slots == 0 with packets
+ * present is an ordinary call: every keyed packet is turned away.
+ * QFEC_CACHED and QFEC_SMALL_GROUPS are accepted and change nothing.  Device
+ * pointers only; the call only queues work on the context's stream, never
+ * waits and never reads anything back.  Its intermediate state lives in the
+ * context-owned scratch of qfec_revive_batch and is rebuilt by every call: a
+ * table of 16-byte entries, a power of two of them and at least twice
+ * n_packets + n_slots, so between 36 and 68 bytes per packet and per slot,
+ * plus 4 bytes per 256 of either and 272 bytes.  The calls that follow on the
+ * same stream reuse the block; stream order makes that safe. */
+#define QFEC_NO_KEY 0xFFFFFFFFFFFFFFFFull /* pkt_key value: this packet is in no FEC group */
+int qfec_assign_slots(qfec_ctx* ctx, const uint64_t* pkt_key, const uint8_t* pkt_k,
+                      uint64_t n_packets, uint64_t* slot_key, uint8_t* slot_k,
+                      const uint16_t* acc_len, uint64_t n_slots, uint32_t* pkt_slot_out,
+                      uint64_t* counts, uint32_t flags);
 
 /* ---- single buffer ------------------------------------------------------ */
 /* out[j] ^= in[j] for j < n (QuicFecGroupInterface::XorBuffers). */
@@ -880,6 +962,11 @@ int qfec_debug_phase_reserve(qfec_ctx* ctx, uint32_t cus);
  * small-batch workers now; *why (nullable) gets why they count (bit 0 a job
  * or warm in the last 2 ms, bit 1 a worker alive, bit 2 its stream busy). */
 uint32_t qfec_debug_other_service_cus(qfec_ctx* ctx, uint32_t* why);
+/* Test hook: mode 1 makes every key of qfec_assign_slots start probing at the
+ * LAST entry of the call's table (one chain through the wrap to entry 0: the
+ * longest probe and the wrap, which no choice of keys reaches from outside);
+ * mode 0 restores the hash.  Results are identical. */
+int qfec_debug_assign_probe(qfec_ctx* ctx, int mode);
 /* Test hook: fail != 0 makes every ragged call on this context fail with
  * QFEC_ERR_INTERNAL before touching the device (the GPU-failure path of the
  * connection integration: groups go without FEC). */

@@ -104,6 +104,7 @@ struct qfec_ctx {
   uint32_t rt_batch = 0;     // test hook (qfec_debug_phase_rtbatch)
   uint32_t phase_reserve = 0;  // test hook (qfec_debug_phase_reserve)
   bool debug_fail = false;   // test hook (qfec_debug_fail_launches)
+  uint32_t assign_probe_last = 0;  // test hook (qfec_debug_assign_probe)
   uint32_t* h_flag = nullptr;
   uint32_t* h_flag_dev = nullptr;
   uint32_t flag_token = 0;
@@ -2405,6 +2406,48 @@ int qfec_bin_arrivals(qfec_ctx* ctx, const uint32_t* pkt_slot, const uint64_t* p
   return revive_scratch_release(ctx);
 }
 
+// QuicConnection::GetFecGroup's group_map_ lookup and insert
+// (quic_connection.cc:1388-1392), for a whole turn: every packet's group key to
+// the slot of its open group, or to a free slot it opens.  One memset and seven
+// kernels on the stream, in the revive calls' scratch; the table they build is
+// this call's alone.
+int qfec_assign_slots(qfec_ctx* ctx, const uint64_t* pkt_key, const uint8_t* pkt_k,
+                      uint64_t n_packets, uint64_t* slot_key, uint8_t* slot_k,
+                      const uint16_t* acc_len, uint64_t n_slots, uint32_t* pkt_slot_out,
+                      uint64_t* counts, uint32_t flags) {
+  const char* const what = "assign slots";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_device_only(ctx, what, flags))) return rc;
+  if (n_packets == 0) return zero_counts(ctx, counts, 5);
+  if (!pkt_key || !pkt_k || !slot_key || !slot_k || !acc_len || !pkt_slot_out)
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: null buffer (only counts may be NULL)", what);
+  if (n_packets >= (1ull << 32) || n_slots >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: 2^32 or more packets or slots (packet and slot indices are 32 bits)", what);
+  if (qfec::assign_table_entries(n_packets, n_slots) == 0)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: more than 2^30 packets and slots together (the call's table is indexed "
+                "with 32 bits)", what);
+  if ((rc = revive_scratch_acquire_bytes(ctx, qfec::assign_scratch_bytes(n_packets, n_slots))))
+    return rc;
+  qfec::AssignArgs a{};
+  a.pkt_key = reinterpret_cast<const unsigned long long*>(pkt_key);
+  a.pkt_k = pkt_k;
+  a.n_packets = n_packets;
+  a.slot_key = reinterpret_cast<unsigned long long*>(slot_key);
+  a.slot_k = slot_k;
+  a.acc_len = acc_len;
+  a.n_slots = (uint32_t)n_slots;
+  a.pkt_slot_out = pkt_slot_out;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.probe_last = ctx->assign_probe_last;
+  a.err = ctx->d_err;
+  a.ncu = ctx->ncu;
+  qfec::assign_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_assign_slots(a, ctx->stream));
+  return revive_scratch_release(ctx);
+}
+
 // qfec_revive_accumulated with the group's K and map kept per slot, where
 // qfec_admit_ragged maintains them.
 int qfec_revive_tracked(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride, uint16_t* acc_len,
@@ -2915,6 +2958,14 @@ int qfec_debug_service_feed(qfec_ctx* ctx, int on, uint64_t* stats) {
 int qfec_debug_fail_launches(qfec_ctx* ctx, int on) {
   if (!ctx) return fail(nullptr, QFEC_ERR_INTERNAL, "null qfec_ctx");
   ctx->debug_fail = on != 0;
+  return QFEC_OK;
+}
+
+int qfec_debug_assign_probe(qfec_ctx* ctx, int mode) {
+  if (!ctx) return fail(nullptr, QFEC_ERR_INTERNAL, "null qfec_ctx");
+  if (mode != 0 && mode != 1)
+    return fail(ctx, QFEC_ERR_INTERNAL, "qfec_debug_assign_probe: mode 0 or 1");
+  ctx->assign_probe_last = (uint32_t)mode;
   return QFEC_OK;
 }
 

@@ -356,6 +356,62 @@ inline void bin_scratch_layout(BinArgs& a, void* block) {
 // ordered by the stream alone.  n_packets > 0, n_slots > 0.
 hipError_t launch_bin_arrivals(const BinArgs& a, hipStream_t s);
 
+// qfec_assign_slots: every packet's 64-bit group key to the slot of its open
+// group, or to a free slot it opens (rule as include/qfec.h).  Scratch, a block
+// of assign_scratch_bytes(n_packets, n_slots) in the revive calls' allocation:
+// an open-addressing table of 16-byte entries (key, value, first arrival) that
+// one memset to 0xFF empties in front of the kernels and nothing keeps between
+// calls; the entry index per packet; the ascending list of free slots; a word
+// per tile of kReviveTile slots and per tile of kReviveTile packets; 16 bytes
+// of totals.
+constexpr unsigned long long kAssignNoKey = 0xFFFFFFFFFFFFFFFFull;  // QFEC_NO_KEY, an empty entry
+constexpr uint32_t kAssignNone = 0xFFFFFFFFu;  // no value, no first arrival, no entry
+struct AssignArgs {
+  const unsigned long long* pkt_key;
+  const uint8_t* pkt_k;
+  uint64_t n_packets;  // 0 < n_packets < 2^32
+  unsigned long long* slot_key;
+  uint8_t* slot_k;
+  const uint16_t* acc_len;
+  uint32_t n_slots;  // may be 0
+  uint32_t* pkt_slot_out;
+  unsigned long long* counts;  // nullable: [open, new, no key, opened, turned away]
+  unsigned long long* table;   // scratch: 2 words per entry (key; value | first << 32)
+  uint32_t cap_mask;           // entries - 1, entries a power of two
+  uint32_t probe_last;         // test hook: every probe starts at the last entry
+  uint32_t* ent;               // scratch: n_packets
+  uint32_t* free_list;         // scratch: n_slots
+  uint32_t* free_tile;         // scratch: 1 per tile of slots
+  uint32_t* open_tile;         // scratch: 1 per tile of packets
+  uint32_t* totals;            // scratch: [free slots] (+ 3 of padding)
+  uint32_t* err;
+  uint32_t ncu;
+};
+// entries: a power of two, at least 16 and at least twice the keys that can be
+// inserted (every open slot's and every packet's); 0 if that passes 2^31 entries
+inline uint64_t assign_table_entries(uint64_t n_packets, uint64_t n_slots) {
+  uint64_t cap = 16;
+  while (cap < 2 * (n_packets + n_slots)) cap <<= 1;
+  return cap <= (1ull << 31) ? cap : 0;
+}
+inline uint64_t assign_scratch_bytes(uint64_t n_packets, uint64_t n_slots) {
+  return assign_table_entries(n_packets, n_slots) * 16 + (n_packets + n_slots) * 4 +
+         (revive_tiles(n_packets) + revive_tiles(n_slots)) * 4 + 16;
+}
+inline void assign_scratch_layout(AssignArgs& a, void* block) {
+  const uint64_t cap = assign_table_entries(a.n_packets, a.n_slots);
+  a.table = static_cast<unsigned long long*>(block);
+  a.cap_mask = (uint32_t)(cap - 1);
+  a.ent = reinterpret_cast<uint32_t*>(a.table + 2 * cap);
+  a.free_list = a.ent + a.n_packets;
+  a.free_tile = a.free_list + a.n_slots;
+  a.open_tile = a.free_tile + revive_tiles(a.n_slots);
+  a.totals = a.open_tile + revive_tiles(a.n_packets);
+}
+// One memset and seven launches on s (slots, probe, tile, scan, free, open,
+// emit), ordered by the stream alone.  n_packets > 0.
+hipError_t launch_assign_slots(const AssignArgs& a, hipStream_t s);
+
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch
 // per batch (the launch is most of a small flush's connection-thread cost).

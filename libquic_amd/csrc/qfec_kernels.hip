@@ -1395,6 +1395,286 @@ __global__ __launch_bounds__(kReviveTile) void bin_order_kernel(BinArgs a) {
 }
 static_assert(kReviveTile == 256, "eight bisection steps; four waves' counts summed by hand");
 
+// ---------------------------------------------------------------------------
+// Group keys to slots (qfec_assign_slots): find each packet's open group or
+// open one in a free slot, in front of the bin.
+// ---------------------------------------------------------------------------
+// Seven kernels on the stream behind one memset to 0xFF of an open-addressing
+// table that lives for this call only (entry: 64-bit key, 32-bit value, 32-bit
+// first arrival; all ones = empty, and QFEC_NO_KEY is never inserted):
+//   slots : one lane per slot; an open slot (acc_len > 0) inserts its key and
+//           takes atomicMin(value, s), so the lowest slot wins; the free slots
+//           of every tile are counted; workgroup 0 zeroes counts;
+//   probe : one lane per packet, one probe per run of neighbouring lanes with
+//           one key: an entry with a value is an open group, complete since
+//           the slots pass; any other is claimed and takes atomicMin(first, p);
+//           the entry index is kept per packet, nothing probes twice;
+//   tile  : the openers (first == p) of every tile of kReviveTile packets;
+//   scan  : one workgroup, exclusive scans over both tile tables in place, the
+//           number of free slots and counts[3];
+//   free  : the ascending list of free slots;
+//   open  : the r-th opener by p takes free[r]: the entry's value, slot_key,
+//           slot_k;
+//   emit  : one lane per packet, pkt_slot_out from the entry's value and the
+//           four packet tallies by ballot, LDS, one atomic per workgroup.
+// The atomics decide only WHICH entry a key lands in; every output is read
+// through the key's own entry, so neither the hash nor the order shows.  Every
+// probe ends after cap steps; every entry index is at most cap_mask by
+// construction (masked) or checked where it is read back from scratch, and
+// every slot read from the table or the free list is checked against n_slots.
+__device__ __forceinline__ uint32_t assign_hash(const AssignArgs& a, unsigned long long k) {
+  k ^= k >> 33;  // (the 64-bit finaliser of MurmurHash3: every key bit reaches the low bits)
+  k *= 0xFF51AFD7ED558CCDull;
+  k ^= k >> 33;
+  k *= 0xC4CEB9FE1A85EC53ull;
+  k ^= k >> 33;
+  return a.probe_last ? a.cap_mask : (uint32_t)k & a.cap_mask;
+}
+__device__ __forceinline__ uint32_t* assign_value(const AssignArgs& a, uint32_t e) {
+  return reinterpret_cast<uint32_t*>(a.table + 2ull * e + 1u);
+}
+__device__ __forceinline__ uint32_t* assign_first(const AssignArgs& a, uint32_t e) {
+  return reinterpret_cast<uint32_t*>(a.table + 2ull * e + 1u) + 1;
+}
+// The entry that holds key, claimed if no entry does; kAssignNone after cap
+// steps without one (a full table: impossible at load 0.5).  The load in front
+// of the compare-and-swap may be stale only as "empty", which the swap corrects.
+__device__ __forceinline__ uint32_t assign_find_or_claim(const AssignArgs& a,
+                                                         unsigned long long key) {
+  uint32_t e = assign_hash(a, key);
+  const uint64_t cap = (uint64_t)a.cap_mask + 1u;
+  for (uint64_t i = 0; i < cap; ++i) {
+    unsigned long long cur =
+        __hip_atomic_load(&a.table[2ull * e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == kAssignNoKey) cur = atomicCAS(&a.table[2ull * e], kAssignNoKey, key);
+    if (cur == kAssignNoKey || cur == key) return e;
+    e = (e + 1u) & a.cap_mask;
+  }
+  return kAssignNone;
+}
+
+__global__ __launch_bounds__(kReviveTile) void assign_slots_kernel(AssignArgs a) {
+  __shared__ uint32_t s_w[kReviveTile / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  if (blockIdx.x == 0u && tid < 5u && a.counts) a.counts[tid] = 0ull;
+  const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const uint64_t s = tile * kReviveTile + tid;
+    const bool in = s < a.n_slots;
+    const uint64_t sc = in ? s : a.n_slots - 1u;  // (clamped, not masked)
+    const bool open = in && a.acc_len[sc] != 0;
+    const unsigned long long key = a.slot_key[sc];
+    if (open && key != kAssignNoKey) {
+      const uint32_t e = assign_find_or_claim(a, key);
+      if (e <= a.cap_mask) atomicMin(assign_value(a, e), (uint32_t)s);
+      else atomicOr(a.err, kErrMissingIndex);
+    }
+    const uint32_t c = (uint32_t)__popcll(__ballot(in && !open));
+    if (lane == 0u) s_w[wave] = c;
+    __syncthreads();
+    if (tid == 0u) a.free_tile[tile] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    __syncthreads();  // s_w is reused by the next tile
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void assign_probe_kernel(AssignArgs a) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const unsigned long long key = a.pkt_key[in ? p : a.n_packets - 1u];  // (clamped, not masked)
+    const bool keyed = in && key != kAssignNoKey;
+    // One probe per RUN of neighbouring lanes with one key (a burst of one
+    // group's packets), made by the run's first lane, which is also the run's
+    // lowest p: the only one whose atomicMin on the first arrival can matter.
+    // Both halves are shuffled by EVERY lane before either is compared: a
+    // shuffle under the && of the comparison runs only in the lanes whose low
+    // halves matched, and reads 0 from a neighbour that is not among them --
+    // equal to the high half of a small key.
+    const uint32_t k_lo = (uint32_t)key, k_hi = (uint32_t)(key >> 32);
+    const uint32_t below_lo = __shfl_up(k_lo, 1), below_hi = __shfl_up(k_hi, 1);
+    const bool same = below_lo == k_lo && below_hi == k_hi;
+    const bool head = keyed && (lane == 0u || !same);
+    const uint64_t heads = __ballot(head);
+    // the last head at or below this lane (32-bit shifts only)
+    const uint32_t m_lo = lane < 32u ? (2u << lane) - 1u : 0xFFFFFFFFu;
+    const uint32_t m_hi = lane < 32u ? 0u : (2u << (lane - 32u)) - 1u;
+    const uint32_t h_lo = (uint32_t)heads & m_lo, h_hi = (uint32_t)(heads >> 32) & m_hi;
+    const uint32_t first = h_hi ? 63u - (uint32_t)__builtin_clz(h_hi)
+                                : (h_lo ? 31u - (uint32_t)__builtin_clz(h_lo) : 0u);
+    uint32_t e = kAssignNone;
+    if (head) {
+      e = assign_find_or_claim(a, key);
+      if (e <= a.cap_mask) {
+        // (the value is final since the slots pass: this kernel never writes it)
+        if (*assign_value(a, e) >= a.n_slots) atomicMin(assign_first(a, e), (uint32_t)p);
+      } else {
+        atomicOr(a.err, kErrMissingIndex);
+      }
+    }
+    e = __shfl(e, first);  // (a keyed lane's run has a head: itself or one below it)
+    if (in) a.ent[p] = keyed ? e : kAssignNone;
+  }
+}
+
+// a packet opens a group if it is the first arrival of an entry that has one
+// (an open group's entry never gets a first arrival)
+__device__ __forceinline__ bool assign_opener(const AssignArgs& a, uint64_t p, uint32_t& e) {
+  e = p < a.n_packets ? a.ent[p] : kAssignNone;
+  return e <= a.cap_mask && *assign_first(a, e) == (uint32_t)p;
+}
+
+__global__ __launch_bounds__(kReviveTile) void assign_tile_kernel(AssignArgs a) {
+  __shared__ uint32_t s_w[kReviveTile / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = (a.n_packets + kReviveTile - 1) / kReviveTile;
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    uint32_t e;
+    const uint32_t c = (uint32_t)__popcll(__ballot(assign_opener(a, tile * kReviveTile + tid, e)));
+    if (lane == 0u) s_w[wave] = c;
+    __syncthreads();
+    if (tid == 0u) a.open_tile[tile] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    __syncthreads();  // s_w is reused by the next tile
+  }
+}
+
+// v[i] = the sum of v[0..i) in place over n words, by one workgroup of
+// kRvScanBlock lanes (every lane reads its own word before it writes it);
+// returns the sum of all.  Sums fit 32 bits: they count packets or slots.
+__device__ __forceinline__ uint32_t assign_scan_in_place(uint32_t* v, uint64_t n, uint32_t* s_sum) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t base = 0;
+  for (uint64_t t0 = 0; t0 < n; t0 += kRvScanBlock) {
+    const uint64_t i = t0 + tid;
+    const uint32_t c = i < n ? v[i] : 0u;
+    uint32_t x = c;  // inclusive scan within the wave
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63u) s_sum[wave] = x;
+    __syncthreads();
+    uint32_t before = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kRvScanBlock / 64; ++w) {
+      if (w < wave) before += s_sum[w];
+      tot += s_sum[w];
+    }
+    if (i < n) v[i] = base + before + (x - c);
+    base += tot;
+    __syncthreads();
+  }
+  return base;
+}
+
+__global__ __launch_bounds__(kRvScanBlock) void assign_scan_kernel(AssignArgs a) {
+  __shared__ uint32_t s_sum[kRvScanBlock / 64];
+  const uint32_t n_free = assign_scan_in_place(
+      a.free_tile, ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile, s_sum);
+  const uint32_t n_open = assign_scan_in_place(
+      a.open_tile, (a.n_packets + kReviveTile - 1) / kReviveTile, s_sum);
+  if (threadIdx.x == 0u) {
+    a.totals[0] = n_free;
+    if (a.counts) a.counts[3] = min(n_free, n_open);  // (zeroed by the slots pass)
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void assign_free_kernel(AssignArgs a) {
+  __shared__ uint32_t s_w[kReviveTile / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const uint64_t s = tile * kReviveTile + tid;
+    const bool in = s < a.n_slots;
+    const bool is_free = in && a.acc_len[in ? s : a.n_slots - 1u] == 0;
+    const uint64_t b = __ballot(is_free);
+    if (lane == 0u) s_w[wave] = (uint32_t)__popcll(b);
+    __syncthreads();
+    // the free slots of the lanes below this one
+    const uint32_t b_lo = (uint32_t)b, b_hi = (uint32_t)(b >> 32);
+    uint32_t pos = lane < 32u ? (uint32_t)__popc(b_lo & ((1u << lane) - 1u))
+                              : (uint32_t)__popc(b_lo) +
+                                    (uint32_t)__popc(b_hi & ((1u << (lane - 32u)) - 1u));
+    for (uint32_t w = 0; w < wave; ++w) pos += s_w[w];
+    const uint64_t r = (uint64_t)a.free_tile[tile] + pos;
+    if (is_free && r < a.n_slots) a.free_list[r] = (uint32_t)s;
+    __syncthreads();  // s_w is reused by the next tile
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void assign_open_kernel(AssignArgs a) {
+  __shared__ uint32_t s_w[kReviveTile / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = (a.n_packets + kReviveTile - 1) / kReviveTile;
+  const uint32_t n_free = min(a.totals[0], a.n_slots);
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const uint64_t p = tile * kReviveTile + tid;
+    uint32_t e;
+    const bool opener = assign_opener(a, p, e);
+    const uint64_t b = __ballot(opener);
+    if (lane == 0u) s_w[wave] = (uint32_t)__popcll(b);
+    __syncthreads();
+    const uint32_t b_lo = (uint32_t)b, b_hi = (uint32_t)(b >> 32);
+    uint32_t pos = lane < 32u ? (uint32_t)__popc(b_lo & ((1u << lane) - 1u))
+                              : (uint32_t)__popc(b_lo) +
+                                    (uint32_t)__popc(b_hi & ((1u << (lane - 32u)) - 1u));
+    for (uint32_t w = 0; w < wave; ++w) pos += s_w[w];
+    const uint64_t r = (uint64_t)a.open_tile[tile] + pos;  // its rank among the openers, by p
+    if (opener && r < n_free) {
+      const uint32_t s = a.free_list[r];
+      if (s < a.n_slots) {
+        *assign_value(a, e) = s;  // (no other lane reads this entry's value in this kernel)
+        a.slot_key[s] = a.pkt_key[p];
+        a.slot_k[s] = a.pkt_k[p];
+      }
+    }
+    __syncthreads();  // s_w is reused by the next tile
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void assign_emit_kernel(AssignArgs a) {
+  __shared__ uint32_t s_w[kReviveTile / 64][4];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t n_old = 0, n_new = 0, n_none = 0, n_away = 0;  // the wave's (uniform)
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const uint64_t pc = in ? p : a.n_packets - 1u;  // (clamped, not masked)
+    const bool keyed = in && a.pkt_key[pc] != kAssignNoKey;
+    const uint32_t e = a.ent[pc];
+    uint32_t s = kAssignNone;
+    bool opened = false;
+    if (keyed && e <= a.cap_mask) {
+      // one 8-byte load: the value and the first arrival
+      const unsigned long long vf = a.table[2ull * e + 1u];
+      s = (uint32_t)vf;
+      opened = (uint32_t)(vf >> 32) != kAssignNone;
+    }
+    const bool placed = s < a.n_slots;
+    if (in) a.pkt_slot_out[p] = placed ? s : kAssignNone;
+    n_old += (uint32_t)__popcll(__ballot(placed && !opened));
+    n_new += (uint32_t)__popcll(__ballot(placed && opened));
+    n_none += (uint32_t)__popcll(__ballot(in && !keyed));
+    n_away += (uint32_t)__popcll(__ballot(keyed && !placed));
+  }
+  if (lane == 0u) {
+    s_w[wave][0] = n_old;
+    s_w[wave][1] = n_new;
+    s_w[wave][2] = n_none;
+    s_w[wave][3] = n_away;
+  }
+  __syncthreads();
+  if (tid < 4u && a.counts) {
+    const uint32_t t = s_w[0][tid] + s_w[1][tid] + s_w[2][tid] + s_w[3][tid];
+    // counts[0..2] and counts[4]; counts[3] is the scan's
+    if (t != 0u) atomicAdd(&a.counts[tid < 3u ? tid : 4u], (unsigned long long)t);
+  }
+}
+static_assert(kReviveTile == 256, "four waves' counts are summed by hand above");
+
 // The recover body over the work list, L >= 16: lanes, windows and loads as
 // fixed_xor_kernel; workgroup step i takes entries [i * gpb, (i + 1) * gpb).
 // `work` and `totals` are separate restrict parameters so that their loads
@@ -3843,6 +4123,34 @@ hipError_t launch_bin_arrivals(const BinArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(bin_scatter_kernel, dim3(pgrid), dim3(kReviveTile), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(bin_order_kernel, dim3(sgrid), dim3(kReviveTile), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_assign_slots(const AssignArgs& a, hipStream_t s) {
+  if (a.n_packets == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(a.table, 0xFF, ((uint64_t)a.cap_mask + 1u) * 16u, s);
+  if (e != hipSuccess) return e;
+  // per packet where a workgroup keeps tallies or only streams: the workgroups
+  // loop, sixteen per CU, as in launch_bin_arrivals; per tile where it scans
+  const uint32_t pgrid = (uint32_t)std::min<uint64_t>(
+      revive_tiles(a.n_packets), (uint64_t)(a.ncu ? a.ncu : 256u) * 16u);
+  const uint32_t ptiles = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_packets), kMaxBlocks256);
+  // (no slots: one workgroup still zeroes counts)
+  const uint32_t stiles = (uint32_t)std::min<uint64_t>(
+      std::max<uint64_t>(revive_tiles(a.n_slots), 1), kMaxBlocks256);
+  hipLaunchKernelGGL(assign_slots_kernel, dim3(stiles), dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(assign_probe_kernel, dim3(pgrid), dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(assign_tile_kernel, dim3(ptiles), dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(assign_scan_kernel, dim3(1), dim3(kRvScanBlock), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(assign_free_kernel, dim3(stiles), dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(assign_open_kernel, dim3(ptiles), dim3(kReviveTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(assign_emit_kernel, dim3(pgrid), dim3(kReviveTile), 0, s, a);
   return hipGetLastError();
 }
 

@@ -38,6 +38,7 @@ QFEC_PKT_FAILED = 1
 QFEC_PKT_DUPLICATE = 2
 QFEC_PKT_INVALID = 3
 QFEC_NO_SLOT = 0xFFFFFFFF
+QFEC_NO_KEY = 0xFFFFFFFFFFFFFFFF
 MAX_PACKET_SIZE = 1452
 DEFAULT_MAX_PACKET_SIZE = 1350
 MAX_GROUP_PACKETS = 255
@@ -103,6 +104,8 @@ SIGNATURES = [
     ("qfec_bin_arrivals", C.c_int,
      [_vp, _vp, _vp, _vp, _u8p, _u8p, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _u8p, _u8p, _vp, _vp,
       C.c_uint32]),
+    ("qfec_assign_slots", C.c_int,
+     [_vp, _vp, _u8p, C.c_uint64, _vp, _u8p, _vp, C.c_uint64, _vp, _vp, C.c_uint32]),
     ("qfec_xor_into", C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint32]),
     ("qfec_wire_write_private_header", C.c_size_t, [_vp, _u8p, C.c_size_t]),
     ("qfec_wire_parse_private_header", C.c_size_t,
@@ -142,6 +145,7 @@ SIGNATURES = [
     ("qfec_last_fixed_phased", C.c_int, [_vp]),
     ("qfec_debug_last_phase_grid", C.c_uint32, [_vp]),
     ("qfec_debug_fail_launches", C.c_int, [_vp, C.c_int]),
+    ("qfec_debug_assign_probe", C.c_int, [_vp, C.c_int]),
     ("qfec_debug_service", C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64)]),
     ("qfec_debug_service_stamps", C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64)]),
     ("qfec_debug_service_trace", C.c_int, [_vp, C.POINTER(C.c_uint64)]),
@@ -586,6 +590,25 @@ class Context:
                                         _ptr(grp_ptr_out), _ptr(pkt_off_out), _ptr(pkt_len_out),
                                         _ptr(pkt_idx_out), _ptr(pkt_ok_out), _ptr(src_out),
                                         _ptr(counts), flags)
+        return self._check(rc)
+
+    def assign_slots(self, pkt_key, pkt_k, n_packets, slot_key, slot_k, acc_len, n_slots,
+                     pkt_slot_out, *, counts=None, flags=0):
+        """qfec_assign_slots: a turn's per-packet group keys in arrival order
+        (pkt_key uint64, opaque, or QFEC_NO_KEY; pkt_k uint8, the group's K,
+        read for a packet that opens a group) resolved to slots: the lowest
+        open slot (acc_len > 0) whose slot_key equals the key, or the next
+        free slot (acc_len == 0, whatever its slot_key) for the r-th new key
+        by first arrival, which writes slot_key (uint64[n_slots]) and slot_k
+        (uint8[n_slots]) there.  pkt_slot_out (uint32[n_packets]) is the
+        pkt_slot bin_arrivals reads; QFEC_NO_SLOT for QFEC_NO_KEY and for a
+        key no free slot was left for.  counts (uint64[5], optional): packets
+        of open groups, packets of groups opened in this call, QFEC_NO_KEY,
+        groups opened, packets turned away.  Device pointers only; queued on
+        the context's stream (sync() before reading the results)."""
+        rc = self.lib.qfec_assign_slots(self.ctx, _ptr(pkt_key), _ptr(pkt_k), n_packets,
+                                        _ptr(slot_key), _ptr(slot_k), _ptr(acc_len), n_slots,
+                                        _ptr(pkt_slot_out), _ptr(counts), flags)
         return self._check(rc)
 
     def xor_into(self, src, n, dst, *, host=False, mapped=False):
