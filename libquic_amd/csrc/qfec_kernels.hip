@@ -307,32 +307,118 @@ __device__ __forceinline__ uint32_t ph_load(uint32_t* w) {
   return __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Meeting number `epoch` (1, 2, ...).  A workgroup adds to one of 16
-// sub-counters (one counter for every workgroup cost ~60 us per meeting at
-// 1,024 adders); the last adder of a sub-counter in this epoch, told by the
-// value its add returned, adds to the top counter, which the waiters poll.
-__device__ __forceinline__ void phase_meet(uint32_t* ps, uint32_t epoch) {
+// Meeting number `epoch` (1, 2, ...), in two parts.
+// Arrive: thread 0 adds its workgroup to one of 16 sub-counters (one counter
+// for every workgroup cost ~60 us per meeting at 1,024 adders); the add's
+// return value tells the last arriver of a sub-counter in this epoch
+// (old + 1 == epoch * nsub), which adds to the top counter (phase_arrived).
+// Wait: the workgroup polls the top counter until it holds epoch * min(B, 16).
+// With kPhEarly = 0 the two run back to back after the phase's last step,
+// behind a read of the abandon flag: three dependent round trips plus the
+// poll, during which the CU neither reads nor writes.  With kPhEarly = E > 0
+// the kernel arrives E steps before the phase's last step, while its loads
+// are in flight, and looks at the returned value one step later, when it is
+// back; phase_wait is then the poll alone (and the top add when the arrival
+// came with the last step).  The fastest workgroups may then start storing
+// while the slowest have up to E steps of reads to go.
+// Invariant (what keeps the epoch arithmetic right with early arrivals): a
+// workgroup arrives for meeting p + 1 only after it has left phase_wait(p),
+// and nobody leaves phase_wait(p) before the top counter says every workgroup
+// has arrived for p, so a sub-counter never holds arrivals of two meetings
+// that are both still open.  The one way out of phase_wait without that is
+// the abandon flag, and a workgroup that has seen it (`gone`, thread 0's)
+// neither arrives nor waits again in this launch.
+// E = 0 / 1 / 2 / 4 at 2^20 groups x 10 x 1350 B, six buffer pairs, fraction
+// of 8 TB/s: encode 0.8268 / 0.8277 / 0.8332 / 0.8415, recover 0.7854 /
+// 0.7898 / 0.7940 / 0.8009; by the stamps a workgroup's wait, summed over a
+// launch's 19 meetings, falls from 100 to 45 us (encode) and from 131 to
+// 103 us (recover), E = 0 to 4; most of it is the workgroups' skew, not the
+// meeting's own round trips (tools/tune/tune_phase.hip,
+// profiles/phase_arrive/tune_phase_arrive.txt).
+constexpr int kPhEarly = 4;  // E: steps before a phase's last step at which a workgroup arrives
+
+__device__ __forceinline__ uint32_t phase_arrive(uint32_t* ps) {
+  return __hip_atomic_fetch_add(ph_word(ps, 1u + (blockIdx.x & 15u)), 1u, __ATOMIC_RELAXED,
+                                __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The early arrival's add: its address passes through a VGPR the compiler
+// cannot see through.  With a uniform address the atomic optimizer rewrites
+// the add as one lane's add of the active-lane count and a readfirstlane of
+// what it returned, with a wait for it right behind the add (found in the
+// assembly: s_waitcnt vmcnt(0) in the arrival step) -- the round trip this
+// arrival is there to hide.
+__device__ __forceinline__ uint32_t phase_arrive_early(uint32_t* ps) {
+  typedef __attribute__((address_space(1))) uint32_t* gptr;  // stays a global access, not flat
+  gptr w = (gptr)ph_word(ps, 1u + (blockIdx.x & 15u));
+  asm volatile("" : "+v"(w));
+  return __hip_atomic_fetch_add(w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// what this workgroup's sub-counter holds when all its workgroups have arrived
+// for meeting `epoch`
+__device__ __forceinline__ uint32_t phase_full(uint32_t epoch) {
+  const uint32_t B = gridDim.x, sub = blockIdx.x & 15u, nsub = (B - sub + 15u) / 16u;
+  return epoch * nsub;
+}
+
+__device__ __forceinline__ void phase_top(uint32_t* ps) {
+  __hip_atomic_fetch_add(ph_word(ps, 0), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// `old`: what this workgroup's phase_arrive for meeting `epoch` returned
+__device__ __forceinline__ void phase_arrived(uint32_t* ps, uint32_t epoch, uint32_t old) {
+  if (old + 1u == phase_full(epoch)) phase_top(ps);
+}
+
+// thread 0: polls the top counter; true when the launch has abandoned its
+// meetings (this workgroup waited kPhTimeout, or another one did)
+__device__ __forceinline__ bool phase_poll(uint32_t* ps, uint32_t epoch) {
+  const uint32_t target = epoch * min(gridDim.x, 16u);
+  const uint64_t t0 = wall_clock64();
+  while (ph_load(ph_word(ps, 0)) < target) {
+    if (wall_clock64() - t0 > kPhTimeout) {
+      if (__hip_atomic_fetch_or(ph_word(ps, 18), 1u, __ATOMIC_RELAXED,
+                                __HIP_MEMORY_SCOPE_AGENT) == 0u)  // count abandoned launches
+        __hip_atomic_fetch_add(ph_word(ps, 19), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return true;
+    }
+    if (ph_load(ph_word(ps, 18)) != 0u) return true;
+    __builtin_amdgcn_s_sleep(1);
+  }
+  return false;
+}
+
+// E = 0: arrive and wait here.  E > 0: the kernel has arrived (`old`); `late`:
+// it has not looked at `old` yet (the arrival came with the phase's last step).
+// T0, T1 (tools/tune only, null in the product): thread 0's clock after the
+// workgroup's last load has returned and when it leaves the meeting.
+template <int E>
+__device__ __forceinline__ void phase_wait(uint32_t* ps, uint32_t epoch, uint32_t old, bool late,
+                                           bool& gone, uint64_t* T0 = nullptr,
+                                           uint64_t* T1 = nullptr) {
   __syncthreads();
-  if (threadIdx.x == 0 && ph_load(ph_word(ps, 18)) == 0u) {
-    const uint32_t B = gridDim.x, sub = blockIdx.x & 15u, nsub = (B - sub + 15u) / 16u;
-    const uint32_t old =
-        __hip_atomic_fetch_add(ph_word(ps, 1u + sub), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old + 1u == epoch * nsub)
-      __hip_atomic_fetch_add(ph_word(ps, 0), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t target = epoch * min(B, 16u);
-    const uint64_t t0 = wall_clock64();
-    while (ph_load(ph_word(ps, 0)) < target) {
-      if (wall_clock64() - t0 > kPhTimeout) {
-        if (__hip_atomic_fetch_or(ph_word(ps, 18), 1u, __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_AGENT) == 0u)  // count abandoned launches
-          __hip_atomic_fetch_add(ph_word(ps, 19), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      if (ph_load(ph_word(ps, 18)) != 0u) break;
-      __builtin_amdgcn_s_sleep(1);
+  if (T0 && threadIdx.x == 0) *T0 = wall_clock64();
+  if constexpr (E == 0) {
+    if (threadIdx.x == 0 && ph_load(ph_word(ps, 18)) == 0u) {
+      phase_arrived(ps, epoch, phase_arrive(ps));
+      gone = phase_poll(ps, epoch);
+    }
+  } else {
+    if (threadIdx.x == 0 && !gone) {
+      if (late) phase_arrived(ps, epoch, old);
+      gone = phase_poll(ps, epoch);
     }
   }
+  if (T1 && threadIdx.x == 0) *T1 = wall_clock64();
   __syncthreads();
+}
+
+// The whole meeting in one call, arrive and wait after the last step: what
+// the persistent kernels of tools/tune that include this file meet with.
+[[maybe_unused]] __device__ __forceinline__ void phase_meet(uint32_t* ps, uint32_t epoch) {
+  bool gone = false;
+  phase_wait<0>(ps, epoch, 0u, false, gone);
 }
 
 // The last workgroup out zeroes the sync words for the next launch on the
@@ -356,7 +442,12 @@ __device__ __forceinline__ void phase_exit(uint32_t* ps, uint32_t* host) {
 // One phase of one workgroup: the first kPhSteps steps keep their parity in
 // LDS, RS more (templated k only) in registers; a step is gpb groups, its k
 // row loads (nontemporal) in flight per lane, one step at a time.  The grid
-// meets once, then every workgroup stores the phase's parity rows.  Step i of
+// meets once, then every workgroup stores the phase's parity rows; a
+// workgroup arrives at that meeting kPhEarly steps before its last step
+// (with step max(SP - kPhEarly, 0) of the launch's SP steps, in the LDS loop
+// or in the register steps) and only waits for the others at the phase's end
+// (phase_arrive / phase_wait above), so the fastest workgroups store while
+// the slowest read their last kPhEarly steps.  Step i of
 // phase p covers one contiguous window of B x gpb groups (the fixed kernel's
 // sliding window), workgroup b its gpb groups at b x gpb.
 //   encode, templated k: the k rows of a step loaded together, XORed.
@@ -395,9 +486,40 @@ __device__ __forceinline__ void phase_exit(uint32_t* ps, uint32_t* host) {
 // profiles/round4/tune_phase_recover_r4l.txt: the register steps' parity rows
 // right after the LDS steps' ones, one parity stream per phase (RPFE), 0.789
 // vs 0.791.
-template <int KC, bool RECOVER, int RS = 0, bool INPL = false, int RTB = 32>
+//
+// QFEC_PHASE_TUNE (tools/tune/tune_phase.hip only; the product build never
+// defines it): E becomes a template parameter, so one process can run several
+// values side by side, and STAMP makes thread 0 of every workgroup write four
+// wall_clock64() stamps per phase into g_phase_stamps[block][phase][4] --
+// 0 the workgroup's last load has returned, 1 it has left the meeting, 2 its
+// last store is issued, 3 the phase's first loads are issued (written at the
+// phase's start, so stamp 2 of phase p pairs with stamp 3 of phase p + 1).
+//
+// The one exception to kPhEarly: the templated recover at k = 24 and 25.  Its
+// 32 unrolled register steps sit just below the size at which the compiler
+// stops unrolling a loop; with the two compares per step of the early
+// arrival it stops, indexes the steps' accumulators at run time and puts them
+// in scratch (528 B; tests/test_isa_guard.py).  These two keep E = 0.
+__host__ __device__ constexpr int phase_early(int kc, bool recover, int rs) {
+  return recover && rs > 0 && kc >= 24 ? 0 : kPhEarly;
+}
+#ifdef QFEC_PHASE_TUNE
+__device__ uint64_t* g_phase_stamps = nullptr;
+#define QFEC_PH_TUNE_TPARAMS , int E = kPhEarly, bool STAMP = false
+#else
+#define QFEC_PH_TUNE_TPARAMS
+#endif
+template <int KC, bool RECOVER, int RS = 0, bool INPL = false, int RTB = 32 QFEC_PH_TUNE_TPARAMS>
 __global__ __launch_bounds__(kBlock) void phase_xor_kernel(FixedArgs a, uint32_t C, uint32_t gpb,
                                                              uint32_t nphase) {
+#ifdef QFEC_PHASE_TUNE
+  uint64_t* const stamps =
+      STAMP && threadIdx.x == 0 ? g_phase_stamps + (uint64_t)blockIdx.x * nphase * 4u : nullptr;
+#else
+  constexpr int E = phase_early(KC, RECOVER, RS);
+  uint64_t* const stamps = nullptr;
+#endif
+  static_assert(E >= 0, "arrival E steps before the phase's last step");
   static_assert(!(INPL && RECOVER), "in place: the encode form over the k rows");
   static_assert(kPhSteps <= 64, "recover: bad-step masks are 64 bits");
   static_assert(RS == 0 || (KC > 0 && RS <= 64), "register steps: templated k, 64-bit lane-on mask");
@@ -413,7 +535,34 @@ __global__ __launch_bounds__(kBlock) void phase_xor_kernel(FixedArgs a, uint32_t
   const uint32_t off = min(t * 16u, a.L - 16u);
   const uint32_t k = KC > 0 ? (uint32_t)KC : a.k;
   const uint64_t B = gridDim.x;
+  // the meeting (above): thread 0 arrives with step `arr`, once that step's
+  // loads are issued, and looks at what the add returned with step arr + 1 (a
+  // wave-uniform compare per step; in a VGPR all the way, no readfirstlane of
+  // a lane-0-only atomic's result: DESIGN.md §13 lesson 8)
+  const int arr = max(SP - E, 0);
+  uint32_t ph_old = 0u;  // thread 0: its arrival's return value
+  bool ph_gone = false;  // thread 0: the launch has abandoned its meetings
   for (uint32_t p = 0; p < nphase; ++p) {
+    // (the step number as this phase's own value: compared with a value that
+    // is the same in every phase, the unrolled register steps' 2 x 32 compare
+    // results are computed once before the phase loop and kept -- 130 more
+    // SGPRs spilled into VGPR lanes, and scratch in the k = 24, 25 recover)
+    int arr_p = arr;
+    if constexpr (E > 0) asm volatile("" : "+s"(arr_p));
+    // (everything a step's share of the meeting needs, once per phase: the
+    // unrolled register steps of the k = 24, 25 recover sit just below the
+    // size at which the compiler stops unrolling them)
+    const bool ph_on = tid == 0u && !ph_gone;
+    const uint32_t ph_full = phase_full(p + 1u);
+    auto early = [&](int step) {
+      if constexpr (E > 0) {
+        if (step == arr_p) {
+          if (ph_on) ph_old = phase_arrive_early(a.phase_sync);
+        } else if (step == arr_p + 1) {
+          if (ph_on && ph_old + 1u == ph_full) phase_top(a.phase_sync);
+        }
+      }
+    };
     const uint64_t base = ((uint64_t)p * (uint64_t)SP * B + blockIdx.x) * gpb + gl;
     // recover: steps whose lost-slot index is out of range (bit i of lo/hi:
     // 32-bit shifts only)
@@ -456,6 +605,7 @@ __global__ __launch_bounds__(kBlock) void phase_xor_kernel(FixedArgs a, uint32_t
           const bool on = i + j < NL && lane_on && g < a.n_groups;
           w[j] = ld16t<true>(a.parity + (on ? g : 0) * a.parity_stride + off);
         }
+        if (stamps && i == 0) stamps[p * 4u + 3u] = wall_clock64();
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           if (i + j < kPhSteps) s_par[i + j][tid] = w[j];
@@ -493,6 +643,7 @@ __global__ __launch_bounds__(kBlock) void phase_xor_kernel(FixedArgs a, uint32_t
           for (int r = 0; r + 1 < KC; ++r)
             v[r] = ld16t<true>(src[u] + ((uint32_t)r + ((uint32_t)r >= m[u] ? 1u : 0u)) * a.row_stride);
           v[KC - 1] = u32x4{0u, 0u, 0u, 0u};
+          early(i + u);
           acc[u] = s_par[i + u][tid];
 #pragma unroll
           for (int r = 0; r < KC; ++r) acc[u] ^= v[r];
@@ -500,9 +651,15 @@ __global__ __launch_bounds__(kBlock) void phase_xor_kernel(FixedArgs a, uint32_t
           u32x4 v[KC];
 #pragma unroll
           for (int r = 0; r < KC; ++r) v[r] = ld16t<true>(src[u] + r * a.row_stride);
+          if (stamps && i + u == 0) stamps[p * 4u + 3u] = wall_clock64();
+          early(i + u);
 #pragma unroll
           for (int r = 0; r < KC; ++r) acc[u] ^= v[r];
         } else {
+          // (runtime k: the step's loads go in batches, so the arrival is
+          // issued ahead of them)
+          if (stamps && i + u == 0) stamps[p * 4u + 3u] = wall_clock64();
+          early(i + u);
           const uint64_t g = gidx(i + u);
           const uint8_t* par = RECOVER ? a.parity + (lane_on && g < a.n_groups ? g : 0) * a.parity_stride + off
                                        : nullptr;
@@ -567,6 +724,7 @@ __global__ __launch_bounds__(kBlock) void phase_xor_kernel(FixedArgs a, uint32_t
 #pragma unroll
           for (int r = 0; r < KC; ++r) v[r] = ld16t<true>(qq + r * a.row_stride);
         }
+        early(kPhSteps + j);
         ron[j / 32] |= on ? 1u << (j % 32) : 0u;
         u32x4 x = v[0];
 #pragma unroll
@@ -585,7 +743,8 @@ __global__ __launch_bounds__(kBlock) void phase_xor_kernel(FixedArgs a, uint32_t
     if constexpr (RECOVER) {
       if (((bad_lo | bad_hi) != 0u || rbad) && t == 0u) atomicOr(a.err, kErrMissingIndex);
     }
-    phase_meet(a.phase_sync, p + 1u);
+    phase_wait<E>(a.phase_sync, p + 1u, ph_old, arr + 1 >= SP, ph_gone, stamps ? stamps + p * 4u : nullptr,
+                  stamps ? stamps + p * 4u + 1u : nullptr);
     // INPL: the output row of group g is its own row missing[g] (the in-slot
     // recover written in place; every read of the phase is done by now, and
     // no other workgroup reads this group).  It runs at 0.73-0.76 of 8 TB/s
@@ -626,6 +785,7 @@ __global__ __launch_bounds__(kBlock) void phase_xor_kernel(FixedArgs a, uint32_t
     if constexpr (INPL) {
       if (ibad && t == 0u) atomicOr(a.err, kErrMissingIndex);
     }
+    if (stamps) stamps[p * 4u + 2u] = wall_clock64();
   }
   phase_exit(a.phase_sync, a.phase_host);
 }

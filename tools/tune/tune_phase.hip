@@ -15,7 +15,18 @@
 // only, 2 = before and after.  Compared with the product kernel over 2 row
 // buffers x 3 parity buffers, interleaved, one process; every variant's
 // parity is compared with the product's.
+//
+// The meeting itself (phase_arrive / phase_wait in the kernel file): the
+// product's k = 10 kernels with the arrival E = 0 (arrive and wait after the
+// last step), 1, 2 and 4 steps before a phase's last step, every one compared
+// byte for byte with the one-pass kernel, then timed with the other variants;
+// and, with stamps (QFEC_PHASE_TUNE: four wall_clock64() stamps per workgroup
+// and phase), a table per E of "last load returned -> meeting left" per
+// phase (mean and maximum over workgroups), the skew of the arrivals, and
+// the sums over the launch.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/tune/tune_phase.hip -o tools/tune/build/tune_phase
+// run:   tune_phase [launches per cell] [rounds] [groups]
+#define QFEC_PHASE_TUNE 1
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
 
 #include <algorithm>
@@ -295,6 +306,37 @@ int main(int argc, char** argv) {
       {"prod 256 x 40+56", qfec::phase_xor_kernel<10, false, 56>},
       {"prod 256 x 40+48", qfec::phase_xor_kernel<10, false, 48>},
   };
+  // the meeting's arrival E steps before a phase's last step (E = 0: today's
+  // arrive-and-wait after the last step), and the same kernels with stamps
+  const int kEs[4] = {0, 1, 2, 4};
+  const PK pk_e[2][4] = {{qfec::phase_xor_kernel<10, false, 32, false, 32, 0>,
+                          qfec::phase_xor_kernel<10, false, 32, false, 32, 1>,
+                          qfec::phase_xor_kernel<10, false, 32, false, 32, 2>,
+                          qfec::phase_xor_kernel<10, false, 32, false, 32, 4>},
+                         {qfec::phase_xor_kernel<10, true, 32, false, 32, 0>,
+                          qfec::phase_xor_kernel<10, true, 32, false, 32, 1>,
+                          qfec::phase_xor_kernel<10, true, 32, false, 32, 2>,
+                          qfec::phase_xor_kernel<10, true, 32, false, 32, 4>}};
+  const PK pk_st[2][4] = {{qfec::phase_xor_kernel<10, false, 32, false, 32, 0, true>,
+                           qfec::phase_xor_kernel<10, false, 32, false, 32, 1, true>,
+                           qfec::phase_xor_kernel<10, false, 32, false, 32, 2, true>,
+                           qfec::phase_xor_kernel<10, false, 32, false, 32, 4, true>},
+                          {qfec::phase_xor_kernel<10, true, 32, false, 32, 0, true>,
+                           qfec::phase_xor_kernel<10, true, 32, false, 32, 1, true>,
+                           qfec::phase_xor_kernel<10, true, 32, false, 32, 2, true>,
+                           qfec::phase_xor_kernel<10, true, 32, false, 32, 4, true>}};
+  const int w_e0 = (int)pks.size();  // pks[w_e0 + 4 * recover + e]
+  for (int rc = 0; rc < 2; ++rc)
+    for (int e = 0; e < 4; ++e)
+      pks.push_back({std::string(rc ? "recover 40+32 E=" : "encode 40+32 E=") + std::to_string(kEs[e]),
+                     pk_e[rc][e]});
+  const int w_st0 = (int)pks.size();  // the stamped kernels: not in the timed table
+  for (int rc = 0; rc < 2; ++rc)
+    for (int e = 0; e < 4; ++e)
+      pks.push_back({std::string(rc ? "recover 40+32 stamps E=" : "encode 40+32 stamps E=") +
+                         std::to_string(kEs[e]),
+                     pk_st[rc][e]});
+  const int w_1p = (int)pks.size();
   pks.push_back({"prod recover one-pass", nullptr});
   uint8_t* d_miss;
   CK(hipMalloc(&d_miss, G));
@@ -303,6 +345,13 @@ int main(int argc, char** argv) {
     for (uint64_t g = 0; g < G; ++g) hm[g] = (uint8_t)((g * 2654435761u >> 7) % kK);
     CK(hipMemcpy(d_miss, hm.data(), G, hipMemcpyHostToDevice));
   }
+  // the stamped kernels' buffer: [workgroup][phase][4] (40 + 32 steps per phase)
+  const uint32_t st_nph = (uint32_t)((G + (uint64_t)ncu * 72 * 3 - 1) / ((uint64_t)ncu * 72 * 3));
+  const size_t st_n = (size_t)ncu * st_nph * 4;
+  uint64_t* d_stamps;
+  CK(hipMalloc(&d_stamps, st_n * 8));
+  CK(hipMemset(d_stamps, 0, st_n * 8));
+  CK(hipMemcpyToSymbol(HIP_SYMBOL(qfec::g_phase_stamps), &d_stamps, sizeof(d_stamps)));
   const uint32_t pnph = (uint32_t)((G + (uint64_t)ncu * 40 * 3 - 1) / ((uint64_t)ncu * 40 * 3));
   auto prod_variant = [&](int w, int i, int j) {
     qfec::FixedArgs a{};
@@ -393,6 +442,28 @@ int main(int argc, char** argv) {
       }
     }
   }
+  // the arrival variants' revived rows against the one-pass recover (their
+  // parity was compared with the one-pass encode above, with every encode)
+  for (int i = 0; i < NR; ++i) {
+    CK(hipMemset(par[1], 0, par_b));
+    prod_variant(w_1p, i, 1);
+    CK(hipMemcpy(want, par[1], par_b, hipMemcpyDeviceToDevice));
+    for (int w = w_e0 + 4; w < w_1p; ++w) {
+      if (pks[w].first.find("recover") == std::string::npos) continue;
+      CK(hipMemset(par[1], 0, par_b));
+      prod_variant(w, i, 1);
+      CK(hipMemset(bad, 0, 4));
+      hipLaunchKernelGGL(count_diff, dim3(4096), dim3(256), 0, 0, par[1], want, par_b, bad);
+      uint32_t h = 0;
+      CK(hipMemcpy(&h, bad, 4, hipMemcpyDeviceToHost));
+      if (h) std::printf("%s rows%d: %u words differ from one-pass\n", pks[w].first.c_str(), i, h);
+    }
+  }
+  {
+    uint32_t ab = 0;
+    CK(hipMemcpy(&ab, psync + 64 * 19, 4, hipMemcpyDeviceToHost));
+    std::printf("abandoned launches so far: %u\n", ab);
+  }
   std::printf("exactness checked (silence = every variant equals the product)\n");
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
@@ -435,14 +506,66 @@ int main(int argc, char** argv) {
                          : v == (int)vs.size()     ? "product one-pass"
                          : v == (int)vs.size() + 1 ? "product phased"
                                                    : pks[v - vs.size() - 2].first.c_str());
+    double mean = 0;
     for (int i = 0; i < NR; ++i)
       for (int j = 0; j < NP; ++j) {
         auto x = res[(v * NR + i) * NP + j];
         std::sort(x.begin(), x.end());
         std::printf(" %.4f", x[x.size() / 2]);
+        mean += x[x.size() / 2] / (NR * NP);
       }
-    std::printf("\n");
+    std::printf("  mean %.4f\n", mean);
   }
   std::printf("phase-wait timeouts (all variants, all launches): %u\n", h_tmo);
+
+  // The meeting by stamps (100 MHz ticks -> us): per phase, over workgroups,
+  // the wait "last load returned -> meeting left" (mean, max), the skew of
+  // "last load returned" (first to last workgroup), and "last store issued ->
+  // next phase's first loads issued"; the third launch of each kernel on
+  // buffer pair r0/p0.
+  {
+    std::vector<uint64_t> hs(st_n);
+    const double us = 0.01;
+    for (int rc = 0; rc < 2; ++rc)
+      for (int e = 0; e < 4; ++e) {
+        const int w = w_st0 + 4 * rc + e;
+        for (int q = 0; q < 3; ++q) prod_variant(w, 0, 0);
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(hs.data(), d_stamps, st_n * 8, hipMemcpyDeviceToHost));
+        auto S = [&](int b, uint32_t p, int s) { return hs[((size_t)b * st_nph + p) * 4 + s]; };
+        uint64_t t_first = ~0ull, t_last = 0;
+        for (int b = 0; b < ncu; ++b) {
+          t_first = std::min(t_first, S(b, 0, 3));
+          t_last = std::max(t_last, S(b, st_nph - 1, 2));
+        }
+        std::printf("\n%s: %u phases, %d workgroups; us\n phase  wait mean  wait max      skew  "
+                    "store->load mean\n",
+                    pks[w].first.c_str(), st_nph, ncu);
+        double sum_mean = 0, sum_max = 0, sum_skew = 0, sum_gap = 0;
+        for (uint32_t p = 0; p < st_nph; ++p) {
+          double mean = 0, mx = 0, gap = 0;
+          uint64_t a0 = ~0ull, a1 = 0;
+          for (int b = 0; b < ncu; ++b) {
+            const double wt = (double)(S(b, p, 1) - S(b, p, 0)) * us;
+            mean += wt / ncu;
+            mx = std::max(mx, wt);
+            a0 = std::min(a0, S(b, p, 0));
+            a1 = std::max(a1, S(b, p, 0));
+            if (p + 1 < st_nph) gap += (double)(S(b, p + 1, 3) - S(b, p, 2)) * us / ncu;
+          }
+          const double skew = (double)(a1 - a0) * us;
+          std::printf(" %5u %10.2f %9.2f %9.2f %17.2f\n", p, mean, mx, skew, gap);
+          sum_mean += mean;
+          sum_max += mx;
+          sum_skew += skew;
+          sum_gap += gap;
+        }
+        const double span = (double)(t_last - t_first) * us;
+        std::printf("   sum %10.2f %9.2f %9.2f %17.2f\n first load issued -> last store issued: "
+                    "%.1f us; summed mean wait %.2f%% of it, summed skew %.2f%%\n",
+                    sum_mean, sum_max, sum_skew, sum_gap, span, 100.0 * sum_mean / span,
+                    100.0 * sum_skew / span);
+      }
+  }
   return 0;
 }
