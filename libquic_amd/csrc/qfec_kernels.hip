@@ -825,6 +825,180 @@ __global__ __launch_bounds__(kBlock) void fixed_small_kernel(FixedArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// Workgroup primitives of the turn passes.
+// ---------------------------------------------------------------------------
+// The scans, sums and ranks in which the passes of the receiver's turn (revive,
+// admit, bin, assign) are written; the ragged kernels further down use the
+// first four.  One contract for all of them: they are called from
+// block-uniform control flow with every lane of every wave active (they
+// shuffle, ballot or meet at a barrier), lane and wave are tid & 63 and
+// tid >> 6, and they shift 32-bit words only (the gfx950 64-bit shift hazard,
+// DESIGN.md §4).  One that takes an LDS array s_w ends with the barrier that
+// makes s_w free again: the caller puts none between two of them.
+constexpr int kTurnWaves = kReviveTile / 64;  // waves of a per-tile or per-packet workgroup
+constexpr int kRvScanBlock = 1024;            // lanes of a one-workgroup scan kernel
+
+__device__ __forceinline__ uint32_t lane_id() {
+  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+}
+
+// Lane src's x (ds_bpermute; src in [0, 64)).  The shuffles below take the
+// caller's lane instead of HIP's __shfl*, which recompute it (mbcnt) and
+// whose lane-derived addresses the compiler hoists out of a resident loop:
+// in the service worker they stayed live through the whole job body and
+// spilled to scratch at 256 VGPRs (round 6).
+__device__ __forceinline__ uint32_t lane_read(uint32_t x, uint32_t src) {
+  return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)x);
+}
+
+// Inclusive prefix sum over the wave.
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t y = lane_read(x, lane >= (uint32_t)d ? lane - (uint32_t)d : lane);
+    if (lane >= (uint32_t)d) x += y;
+  }
+  return x;
+}
+
+// Exclusive prefix sum over a workgroup of WAVES waves, and the sum of all.
+template <int WAVES>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t lane, uint32_t wv,
+                                                    uint32_t* s_w, uint32_t& total) {
+  const uint32_t incl = wave_incl_scan(x, lane);
+  if (lane == 63u) s_w[wv] = incl;
+  __syncthreads();
+  uint32_t base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) {
+    const uint32_t v = s_w[w];
+    base += (uint32_t)w < wv ? v : 0u;
+    tot += v;
+  }
+  total = tot;
+  __syncthreads();  // s_w free again
+  return base + incl - x;
+}
+
+// put(i, the sum of get(0 .. i - 1)) for every i < n by one workgroup of
+// kRvScanBlock lanes, a trip per kRvScanBlock elements with the running base in
+// a register; returns the sum of all.  An element is a 32-bit count and so is
+// the sum of a trip; s_w: kRvScanBlock / 64 words.  get(i) is called exactly
+// once for every i < n, by the lane that then puts i and before it does: in
+// place is fine, and a get may keep sums of its own per lane on the way (the
+// side totals of the revive's and the admit's scan).  No barrier if n == 0.
+template <typename Get, typename Put>
+__device__ __forceinline__ uint64_t tile_scan(uint64_t n, uint32_t* s_w, Get get, Put put) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint64_t base = 0;
+  for (uint64_t t0 = 0; t0 < n; t0 += kRvScanBlock) {
+    const uint64_t i = t0 + tid;
+    uint32_t tot;
+    const uint32_t before =
+        block_excl_scan<kRvScanBlock / 64>(i < n ? get(i) : 0u, lane, wave, s_w, tot);
+    if (i < n) put(i, base + before);
+    base += tot;
+  }
+  return base;
+}
+// ... over the n words of v in place (sums that fit 32 bits: packets or slots)
+__device__ __forceinline__ uint32_t tile_scan_in_place(uint32_t* v, uint64_t n, uint32_t* s_w) {
+  return (uint32_t)tile_scan(
+      n, s_w, [=](uint64_t i) { return v[i]; }, [=](uint64_t i, uint64_t x) { v[i] = (uint32_t)x; });
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+// Every wave of a kTurnWaves-wave workgroup brings CH counts (uniform in the
+// wave: ballot popcounts, wave_sums); lane ch < CH of every wave gets the
+// workgroup's sum of count ch (the lanes above it that of the last: a clamped
+// read, not a masked one).  s_w: kTurnWaves * CH words.
+template <int CH>
+__device__ __forceinline__ uint32_t block_sum(const uint32_t (&c)[CH], uint32_t lane,
+                                              uint32_t wave, uint32_t* s_w) {
+  if (lane == 0u) {
+#pragma unroll
+    for (int ch = 0; ch < CH; ++ch) s_w[wave * CH + ch] = c[ch];
+  }
+  __syncthreads();
+  const uint32_t ch = min(lane, (uint32_t)(CH - 1));
+  uint32_t t = 0;
+#pragma unroll
+  for (int w = 0; w < kTurnWaves; ++w) t += s_w[w * CH + ch];
+  __syncthreads();  // s_w free again
+  return t;
+}
+__device__ __forceinline__ uint32_t block_sum(uint32_t c, uint32_t lane, uint32_t wave,
+                                              uint32_t* s_w) {
+  const uint32_t one[1] = {c};
+  return block_sum(one, lane, wave, s_w);
+}
+
+// The set bits of ballot b below this lane (v_mbcnt: no shift, no lane).
+__device__ __forceinline__ uint32_t ballot_rank(uint64_t b) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32),
+                                   __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+}
+
+// ... and below it in the whole kTurnWaves-wave workgroup, b being each wave's
+// ballot of one predicate; total: the workgroup's set bits.
+__device__ __forceinline__ uint32_t block_ballot_rank(uint64_t b, uint32_t lane, uint32_t wave,
+                                                      uint32_t* s_w, uint32_t& total) {
+  if (lane == 0u) s_w[wave] = (uint32_t)__popcll(b);
+  __syncthreads();
+  uint32_t r = ballot_rank(b), tot = 0;
+#pragma unroll
+  for (int w = 0; w < kTurnWaves; ++w) {
+    const uint32_t v = s_w[w];
+    r += (uint32_t)w < wave ? v : 0u;
+    tot += v;
+  }
+  total = tot;
+  __syncthreads();  // s_w free again
+  return r;
+}
+__device__ __forceinline__ uint32_t block_ballot_rank(uint64_t b, uint32_t lane, uint32_t wave,
+                                                      uint32_t* s_w) {
+  uint32_t total;
+  return block_ballot_rank(b, lane, wave, s_w, total);
+}
+
+// Runs of neighbouring lanes with one key, so that a run's first lane can make
+// one atomic or one probe for all of it.  eligible: the lane takes part; same:
+// its key equals that of the lane below.  THE RULE for `same`: every lane
+// executes every shuffle before anything is compared.  A __shfl_up under the &&
+// of a comparison, or under `eligible`, runs only in the lanes that got that
+// far and reads 0 from a neighbour that is not among them, which equals the
+// high half of a small key: 4 of 81,999 packets took the wrong slot that way.
+// head: the lane is the first of a run; first: the head of the lane's run (its
+// last head at or below); end: the lane after the run (the next head or
+// ineligible lane, or 64).  first and end mean something in eligible lanes only.
+struct LaneRun {
+  bool head;
+  uint32_t first, end;
+};
+__device__ __forceinline__ LaneRun lane_runs(bool eligible, bool same, uint32_t lane) {
+  LaneRun r;
+  r.head = eligible && (lane == 0u || !same);
+  const uint64_t heads = __ballot(r.head), enders = heads | ~__ballot(eligible);
+  // the lanes at or below this one, as 32-bit words
+  const uint32_t m_lo = lane < 32u ? (2u << lane) - 1u : 0xFFFFFFFFu;
+  const uint32_t m_hi = lane < 32u ? 0u : (2u << (lane - 32u)) - 1u;
+  const uint32_t h_lo = (uint32_t)heads & m_lo, h_hi = (uint32_t)(heads >> 32) & m_hi;
+  const uint32_t e_lo = (uint32_t)enders & ~m_lo, e_hi = (uint32_t)(enders >> 32) & ~m_hi;
+  r.first = h_hi ? 63u - (uint32_t)__builtin_clz(h_hi)
+                 : (h_lo ? 31u - (uint32_t)__builtin_clz(h_lo) : 0u);
+  r.end = e_lo ? (uint32_t)__builtin_ctz(e_lo)
+               : (e_hi ? 32u + (uint32_t)__builtin_ctz(e_hi) : 64u);
+  return r;
+}
+static_assert(kReviveTile % 64 == 0 && kRvScanBlock % 64 == 0, "whole waves");
+
+// ---------------------------------------------------------------------------
 // Revive from per-group receive maps (qfec_revive_batch).
 // ---------------------------------------------------------------------------
 // A batch in which most groups need nothing: classify every group from its
@@ -844,7 +1018,6 @@ __global__ __launch_bounds__(kBlock) void fixed_small_kernel(FixedArgs a) {
 //              entry i, a grid-stride loop over the list whose length the
 //              kernel reads from scratch (the host never learns it).
 constexpr uint32_t kGroupComplete = 0, kGroupRevived = 1, kGroupUnrevivable = 2;
-constexpr int kRvScanBlock = 1024;
 
 // Status of the group whose map starts at mp; m: its one clear data bit
 // (revived groups only, else 0xFF).  All shifts are 32-bit (the gfx950 64-bit
@@ -1007,7 +1180,7 @@ __device__ __forceinline__ uint64_t revive_emit_group(const Args& a, uint64_t g,
 
 template <bool EMIT, typename Args>
 __global__ __launch_bounds__(kReviveTile) void revive_classify_kernel(Args a) {
-  __shared__ uint32_t s_w[kReviveTile / 64];
+  __shared__ uint32_t s_w[kTurnWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
   for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
@@ -1029,67 +1202,45 @@ __global__ __launch_bounds__(kReviveTile) void revive_classify_kernel(Args a) {
         a.status[g] = (uint8_t)st;
         if (a.revived_idx) a.revived_idx[g] = (uint8_t)m;
       }
-      if (lane == 0u) s_w[wave] = (uint32_t)__popcll(brev) | ((uint32_t)__popcll(bcomp) << 16);
-      __syncthreads();
-      if (tid == 0u) a.tile_cnt[tile] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+      const uint32_t t = block_sum(
+          (uint32_t)__popcll(brev) | ((uint32_t)__popcll(bcomp) << 16), lane, wave, s_w);
+      if (tid == 0u) a.tile_cnt[tile] = t;
     } else {
-      if (lane == 0u) s_w[wave] = (uint32_t)__popcll(brev);
-      __syncthreads();
+      // (its loads and stores go out in front of the rank's two barriers)
       const uint64_t ex = revive_emit_group(a, g, st);
+      const uint32_t rank = block_ballot_rank(brev, lane, wave, s_w);
       if (st == kGroupRevived) {
-        uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(brev >> 32),
-                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)brev, 0u));
-        for (uint32_t w = 0; w < wave; ++w) rank += s_w[w];
         const uint64_t pos = a.tile_off[tile] + rank;
         a.work[pos] = (g << 8) | m | ex;
         if (a.revived_list) a.revived_list[pos] = g;
       }
     }
-    __syncthreads();  // s_w is reused by the next tile
   }
 }
-static_assert(kReviveTile == 256, "four waves' counts are summed by hand above");
 
 // One workgroup: tile_off[i] = revived groups in tiles before i, then the
-// totals.  A tile of the scan is kRvScanBlock counts; the running bases are
-// uniform registers.
+// totals.  The complete groups are a sum per lane, then per wave through s_w
+// (a wave's sixteenth of the groups fits 32 bits: the work list of 2^36 groups
+// would be 512 GiB).
 template <typename Args>
 __global__ __launch_bounds__(kRvScanBlock) void revive_scan_kernel(Args a) {
-  __shared__ uint32_t s_rev[kRvScanBlock / 64], s_comp[kRvScanBlock / 64];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
-  uint64_t base_rev = 0, base_comp = 0;
-  for (uint64_t t0 = 0; t0 < ntile; t0 += kRvScanBlock) {
-    const uint64_t i = t0 + tid;
-    const uint32_t c = i < ntile ? a.tile_cnt[i] : 0u;
-    const uint32_t rev = c & 0xFFFFu, comp = c >> 16;
-    uint32_t xr = rev, xc = comp;  // inclusive scans within the wave
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t yr = __shfl_up(xr, d), yc = __shfl_up(xc, d);
-      if (lane >= d) {
-        xr += yr;
-        xc += yc;
-      }
-    }
-    if (lane == 63u) {
-      s_rev[wave] = xr;
-      s_comp[wave] = xc;
-    }
-    __syncthreads();
-    uint32_t before = 0, tot_rev = 0, tot_comp = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kRvScanBlock / 64; ++w) {
-      if (w < wave) before += s_rev[w];
-      tot_rev += s_rev[w];
-      tot_comp += s_comp[w];
-    }
-    if (i < ntile) a.tile_off[i] = base_rev + before + (xr - rev);
-    base_rev += tot_rev;
-    base_comp += tot_comp;
-    __syncthreads();
-  }
+  __shared__ uint32_t s_w[kRvScanBlock / 64];
+  const uint32_t tid = threadIdx.x;
+  uint32_t comp = 0;
+  const uint64_t base_rev = tile_scan(
+      (a.n_groups + kReviveTile - 1) / kReviveTile, s_w,
+      [&](uint64_t i) {
+        const uint32_t c = a.tile_cnt[i];
+        comp += c >> 16;
+        return c & 0xFFFFu;
+      },
+      [&](uint64_t i, uint64_t x) { a.tile_off[i] = x; });
+  comp = wave_sum(comp);
+  if ((tid & 63u) == 0u) s_w[tid >> 6] = comp;
+  __syncthreads();
   if (tid == 0u) {
+    uint64_t base_comp = 0;
+    for (uint32_t w = 0; w < kRvScanBlock / 64; ++w) base_comp += s_w[w];
     const uint64_t unrev = a.n_groups - base_rev - base_comp;
     a.totals[kGroupComplete] = base_comp;
     a.totals[kGroupRevived] = base_rev;
@@ -1124,15 +1275,9 @@ __global__ __launch_bounds__(kRvScanBlock) void revive_scan_kernel(Args a) {
 constexpr uint32_t kPktAdmitted = 0, kPktFailed = 1, kPktDuplicate = 2, kPktInvalid = 3;
 constexpr uint32_t kAdmitMapWords = 8;  // bits 0..K, K <= 255
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
 __global__ __launch_bounds__(kReviveTile) void admit_decide_kernel(AdmitArgs a) {
   __shared__ uint32_t s_map[kAdmitMapWords][kReviveTile];  // word-major: no bank conflicts
-  __shared__ uint32_t s_w[kReviveTile / 64][4];
+  __shared__ uint32_t s_w[kTurnWaves * 4];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
   for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
@@ -1208,56 +1353,31 @@ __global__ __launch_bounds__(kReviveTile) void admit_decide_kernel(AdmitArgs a) 
       if (bad != 0u) atomicOr(a.err, bad);
       a.grp_cnt[g] = c_adm;
     }
-    const uint32_t w_adm = wave_sum(c_adm), w_fail = wave_sum(c_fail), w_dup = wave_sum(c_dup),
-                   w_inv = wave_sum(c_inv);
-    if (lane == 0u) {
-      s_w[wave][kPktAdmitted] = w_adm;
-      s_w[wave][kPktFailed] = w_fail;
-      s_w[wave][kPktDuplicate] = w_dup;
-      s_w[wave][kPktInvalid] = w_inv;
-    }
-    __syncthreads();
-    if (tid < 4u) a.tile_v[tile * 4u + tid] = s_w[0][tid] + s_w[1][tid] + s_w[2][tid] + s_w[3][tid];
-    __syncthreads();  // s_w is reused by the next tile
+    // (in the order of the verdicts: kPktAdmitted, Failed, Duplicate, Invalid)
+    const uint32_t c[4] = {wave_sum(c_adm), wave_sum(c_fail), wave_sum(c_dup), wave_sum(c_inv)};
+    const uint32_t t = block_sum(c, lane, wave, s_w);
+    if (tid < 4u) a.tile_v[tile * 4u + tid] = t;
   }
 }
 
 // One workgroup: tile_off[i] = packets admitted in the tiles before i, then
-// the totals.
+// the totals.  The other three verdicts are sums per lane, met in LDS at the end.
 __global__ __launch_bounds__(kRvScanBlock) void admit_scan_kernel(AdmitArgs a) {
-  __shared__ uint32_t s_adm[kRvScanBlock / 64];
+  __shared__ uint32_t s_w[kRvScanBlock / 64];
   __shared__ unsigned long long s_tot[3];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
-  if (tid < 3u) s_tot[tid] = 0ull;
-  uint64_t base = 0, fail = 0, dup = 0, inv = 0;
-  for (uint64_t t0 = 0; t0 < ntile; t0 += kRvScanBlock) {
-    const uint64_t i = t0 + tid;
-    uint32_t adm = 0;
-    if (i < ntile) {
-      adm = a.tile_v[i * 4u + kPktAdmitted];
-      fail += a.tile_v[i * 4u + kPktFailed];
-      dup += a.tile_v[i * 4u + kPktDuplicate];
-      inv += a.tile_v[i * 4u + kPktInvalid];
-    }
-    uint32_t x = adm;  // inclusive scan within the wave
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t y = __shfl_up(x, d);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63u) s_adm[wave] = x;
-    __syncthreads();
-    uint32_t before = 0, tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kRvScanBlock / 64; ++w) {
-      if (w < wave) before += s_adm[w];
-      tot += s_adm[w];
-    }
-    if (i < ntile) a.tile_off[i] = base + before + (x - adm);
-    base += tot;
-    __syncthreads();
-  }
+  const uint32_t tid = threadIdx.x;
+  if (tid < 3u) s_tot[tid] = 0ull;  // (the scan's barriers lie between this and the
+                                    // sums: n_groups > 0, the launcher's guard)
+  uint64_t fail = 0, dup = 0, inv = 0;
+  const uint64_t base = tile_scan(
+      (a.n_groups + kReviveTile - 1) / kReviveTile, s_w,
+      [&](uint64_t i) {
+        fail += a.tile_v[i * 4u + kPktFailed];
+        dup += a.tile_v[i * 4u + kPktDuplicate];
+        inv += a.tile_v[i * 4u + kPktInvalid];
+        return a.tile_v[i * 4u + kPktAdmitted];
+      },
+      [&](uint64_t i, uint64_t x) { a.tile_off[i] = x; });
   if (fail != 0ull) atomicAdd(&s_tot[0], (unsigned long long)fail);
   if (dup != 0ull) atomicAdd(&s_tot[1], (unsigned long long)dup);
   if (inv != 0ull) atomicAdd(&s_tot[2], (unsigned long long)inv);
@@ -1278,23 +1398,16 @@ __global__ __launch_bounds__(kRvScanBlock) void admit_scan_kernel(AdmitArgs a) {
 // grp_ptr that is not monotone (latched by the decide pass) the valid groups
 // can claim more, and no entry is written past it.
 __global__ __launch_bounds__(kReviveTile) void admit_scatter_kernel(AdmitArgs a) {
-  __shared__ uint32_t s_w[kReviveTile / 64];
+  __shared__ uint32_t s_w[kTurnWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint64_t ntile = (a.n_groups + kReviveTile - 1) / kReviveTile;
   const uint32_t room = a.grp_ptr[a.n_groups] - a.grp_ptr[0];
   for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     const uint64_t g = tile * kReviveTile + tid;
     const uint32_t cnt = g < a.n_groups ? a.grp_cnt[g] : 0u;
-    uint32_t x = cnt;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t y = __shfl_up(x, d);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63u) s_w[wave] = x;
-    __syncthreads();
-    uint32_t pos = (uint32_t)a.tile_off[tile] + (x - cnt);
-    for (uint32_t w = 0; w < wave; ++w) pos += s_w[w];
+    uint32_t tot;
+    const uint32_t pos =
+        (uint32_t)a.tile_off[tile] + block_excl_scan<kTurnWaves>(cnt, lane, wave, s_w, tot);
     uint32_t p0 = 0, kg = 0;
     if (g < a.n_groups) {
       a.grp_ptr_out[g] = pos;
@@ -1306,25 +1419,19 @@ __global__ __launch_bounds__(kReviveTile) void admit_scatter_kernel(AdmitArgs a)
     // packet's place is the tile's plus the admitted packets before it in the
     // run -- one lane per PACKET, loads and stores coalesced (a lane per group
     // touches a cache line per lane and store: 6x the time on 2^20 groups).
-    if (__syncthreads_and(kg <= 255u ? 1 : 0)) {  // (also orders s_w's reads and writes)
+    if (__syncthreads_and(kg <= 255u ? 1 : 0)) {  // (the vote; s_w is free since the scan)
       const uint64_t gend = min((tile + 1) * (uint64_t)kReviveTile, a.n_groups);
       const uint32_t first = a.grp_ptr[tile * kReviveTile], end = a.grp_ptr[gend];
       uint32_t base = (uint32_t)a.tile_off[tile];
       for (uint64_t q = first; q < end; q += kReviveTile) {  // (uniform; 64-bit: no wrap)
         const uint64_t p = q + tid;
         const bool adm = p < end && a.verdict[p] == (uint8_t)kPktAdmitted;
-        const uint64_t b = __ballot(adm);
-        if (lane == 0u) s_w[wave] = (uint32_t)__popcll(b);
-        __syncthreads();
-        uint32_t r = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32),
-                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-        for (uint32_t w = 0; w < wave; ++w) r += s_w[w];
+        const uint32_t r = base + block_ballot_rank(__ballot(adm), lane, wave, s_w, tot);
         if (adm && r < room) {
           a.pkt_off_out[r] = a.pkt_off[p];
           a.pkt_len_out[r] = a.pkt_len[p];
         }
-        base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        __syncthreads();  // s_w is reused by the next step and the next tile
+        base += tot;
       }
     } else {
       // a group of more than 255 candidates in the tile (its verdicts are not
@@ -1339,11 +1446,9 @@ __global__ __launch_bounds__(kReviveTile) void admit_scatter_kernel(AdmitArgs a)
           ++r;
         }
       }
-      __syncthreads();  // s_w is reused by the next tile
     }
   }
 }
-static_assert(kReviveTile == 256, "four waves' counts are summed by hand above");
 
 // ---------------------------------------------------------------------------
 // Arrival order to per-slot CSR tables (qfec_bin_arrivals): a stable counting
@@ -1372,9 +1477,9 @@ static_assert(kReviveTile == 256, "four waves' counts are summed by hand above")
 // pass removes that freedom.  Every index formed from pkt_slot is checked
 // against n_slots first, and every place against n_packets.
 __global__ __launch_bounds__(kReviveTile) void bin_count_kernel(BinArgs a) {
-  __shared__ uint32_t s_w[kReviveTile / 64][3];
+  __shared__ uint32_t s_w[kTurnWaves * 3];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  uint32_t n_bin = 0, n_none = 0, n_bad = 0;  // the wave's (uniform)
+  uint32_t n[3] = {0, 0, 0};  // the wave's binned, slotless and out-of-range packets (uniform)
   const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
   for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
     const uint64_t p = p0 + tid;
@@ -1388,83 +1493,40 @@ __global__ __launch_bounds__(kReviveTile) void bin_count_kernel(BinArgs a) {
     // already grouped cost a tenth of the atomics, a random order what it did.
     // (a binned lane's slot differs from any lane's that is not binned)
     const uint32_t prev = __shfl_up(s, 1);
-    const bool head = binned && (lane == 0u || prev != s);
-    const uint64_t heads = __ballot(head), enders = heads | ~__ballot(binned);
-    // the lanes at or below this one, as 32-bit words (32-bit shifts only)
-    const uint32_t m_lo = lane < 32u ? (2u << lane) - 1u : 0xFFFFFFFFu;
-    const uint32_t m_hi = lane < 32u ? 0u : (2u << (lane - 32u)) - 1u;
-    const uint32_t h_lo = (uint32_t)heads & m_lo, h_hi = (uint32_t)(heads >> 32) & m_hi;
-    const uint32_t e_lo = (uint32_t)enders & ~m_lo, e_hi = (uint32_t)(enders >> 32) & ~m_hi;
-    // its run: from the last head at or below it to the next head or unbinned lane
-    const uint32_t first = h_hi ? 63u - (uint32_t)__builtin_clz(h_hi)
-                                : (h_lo ? 31u - (uint32_t)__builtin_clz(h_lo) : 0u);
-    const uint32_t end = e_lo ? (uint32_t)__builtin_ctz(e_lo)
-                              : (e_hi ? 32u + (uint32_t)__builtin_ctz(e_hi) : 64u);
+    const LaneRun run = lane_runs(binned, prev == s, lane);
     uint32_t base = 0;
-    if (head) base = atomicAdd(&a.cnt[s], end - lane);
-    base = __shfl(base, first);
-    if (binned) a.rank[p] = base + (lane - first);
-    n_bin += (uint32_t)__popcll(__ballot(binned));
-    n_none += (uint32_t)__popcll(__ballot(none));
-    n_bad += (uint32_t)__popcll(__ballot(bad));
+    if (run.head) base = atomicAdd(&a.cnt[s], run.end - lane);
+    base = __shfl(base, run.first);
+    if (binned) a.rank[p] = base + (lane - run.first);
+    n[0] += (uint32_t)__popcll(__ballot(binned));
+    n[1] += (uint32_t)__popcll(__ballot(none));
+    n[2] += (uint32_t)__popcll(__ballot(bad));
   }
-  if (lane == 0u) {
-    s_w[wave][0] = n_bin;
-    s_w[wave][1] = n_none;
-    s_w[wave][2] = n_bad;
-  }
-  __syncthreads();
+  const uint32_t t = block_sum(n, lane, wave, s_w);
   if (tid < 3u) {
-    const uint32_t t = s_w[0][tid] + s_w[1][tid] + s_w[2][tid] + s_w[3][tid];
     if (t != 0u) atomicAdd(&a.tally[tid], (unsigned long long)t);
     if (tid == 2u && t != 0u) atomicOr(a.err, kErrMissingIndex);
   }
 }
 
 __global__ __launch_bounds__(kReviveTile) void bin_tile_kernel(BinArgs a) {
-  __shared__ uint32_t s_w[kReviveTile / 64];
+  __shared__ uint32_t s_w[kTurnWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
   for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     const uint64_t s = tile * kReviveTile + tid;
-    const uint32_t c = wave_sum(s < a.n_slots ? a.cnt[s] : 0u);
-    if (lane == 0u) s_w[wave] = c;
-    __syncthreads();
-    if (tid == 0u) a.tile_off[tile] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();  // s_w is reused by the next tile
+    const uint32_t t = block_sum(wave_sum(s < a.n_slots ? a.cnt[s] : 0u), lane, wave, s_w);
+    if (tid == 0u) a.tile_off[tile] = t;
   }
 }
 
 // One workgroup: tile_off[i] = packets binned to the tiles before i (in place
-// over the tile sums: every lane reads its own word before it writes it), then
-// the totals.  All sums fit 32 bits: n_packets < 2^32.
+// over the tile sums), then the totals.  All sums fit 32 bits: n_packets < 2^32.
 __global__ __launch_bounds__(kRvScanBlock) void bin_scan_kernel(BinArgs a) {
-  __shared__ uint32_t s_sum[kRvScanBlock / 64];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
-  uint32_t base = 0;
-  for (uint64_t t0 = 0; t0 < ntile; t0 += kRvScanBlock) {
-    const uint64_t i = t0 + tid;
-    const uint32_t c = i < ntile ? a.tile_off[i] : 0u;
-    uint32_t x = c;  // inclusive scan within the wave
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t y = __shfl_up(x, d);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63u) s_sum[wave] = x;
-    __syncthreads();
-    uint32_t before = 0, tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kRvScanBlock / 64; ++w) {
-      if (w < wave) before += s_sum[w];
-      tot += s_sum[w];
-    }
-    if (i < ntile) a.tile_off[i] = base + before + (x - c);
-    base += tot;
-    __syncthreads();
-  }
-  if (tid == 0u) {
+  __shared__ uint32_t s_w[kRvScanBlock / 64];
+  const uint32_t base = tile_scan_in_place(
+      a.tile_off, ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile, s_w);
+  if (threadIdx.x == 0u) {
     a.grp_ptr_out[a.n_slots] = base;
     if (a.counts) {
       a.counts[0] = a.tally[0];
@@ -1475,24 +1537,15 @@ __global__ __launch_bounds__(kRvScanBlock) void bin_scan_kernel(BinArgs a) {
 }
 
 __global__ __launch_bounds__(kReviveTile) void bin_ptr_kernel(BinArgs a) {
-  __shared__ uint32_t s_w[kReviveTile / 64];
+  __shared__ uint32_t s_w[kTurnWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
   for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     const uint64_t s = tile * kReviveTile + tid;
-    const uint32_t c = s < a.n_slots ? a.cnt[s] : 0u;
-    uint32_t x = c;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t y = __shfl_up(x, d);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63u) s_w[wave] = x;
-    __syncthreads();
-    uint32_t pos = a.tile_off[tile] + (x - c);
-    for (uint32_t w = 0; w < wave; ++w) pos += s_w[w];
-    if (s < a.n_slots) a.grp_ptr_out[s] = pos;
-    __syncthreads();  // s_w is reused by the next tile
+    uint32_t tot;
+    const uint32_t before =
+        block_excl_scan<kTurnWaves>(s < a.n_slots ? a.cnt[s] : 0u, lane, wave, s_w, tot);
+    if (s < a.n_slots) a.grp_ptr_out[s] = a.tile_off[tile] + before;
   }
 }
 
@@ -1553,7 +1606,7 @@ __global__ __launch_bounds__(kReviveTile) void bin_order_kernel(BinArgs a) {
     __syncthreads();  // s_ptr is reused by the next tile
   }
 }
-static_assert(kReviveTile == 256, "eight bisection steps; four waves' counts summed by hand");
+static_assert(kReviveTile == 256, "eight bisection steps");
 
 // ---------------------------------------------------------------------------
 // Group keys to slots (qfec_assign_slots): find each packet's open group or
@@ -1614,7 +1667,7 @@ __device__ __forceinline__ uint32_t assign_find_or_claim(const AssignArgs& a,
 }
 
 __global__ __launch_bounds__(kReviveTile) void assign_slots_kernel(AssignArgs a) {
-  __shared__ uint32_t s_w[kReviveTile / 64];
+  __shared__ uint32_t s_w[kTurnWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   if (blockIdx.x == 0u && tid < 5u && a.counts) a.counts[tid] = 0ull;
   const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
@@ -1629,11 +1682,8 @@ __global__ __launch_bounds__(kReviveTile) void assign_slots_kernel(AssignArgs a)
       if (e <= a.cap_mask) atomicMin(assign_value(a, e), (uint32_t)s);
       else atomicOr(a.err, kErrMissingIndex);
     }
-    const uint32_t c = (uint32_t)__popcll(__ballot(in && !open));
-    if (lane == 0u) s_w[wave] = c;
-    __syncthreads();
-    if (tid == 0u) a.free_tile[tile] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();  // s_w is reused by the next tile
+    const uint32_t t = block_sum((uint32_t)__popcll(__ballot(in && !open)), lane, wave, s_w);
+    if (tid == 0u) a.free_tile[tile] = t;
   }
 }
 
@@ -1648,23 +1698,12 @@ __global__ __launch_bounds__(kReviveTile) void assign_probe_kernel(AssignArgs a)
     // One probe per RUN of neighbouring lanes with one key (a burst of one
     // group's packets), made by the run's first lane, which is also the run's
     // lowest p: the only one whose atomicMin on the first arrival can matter.
-    // Both halves are shuffled by EVERY lane before either is compared: a
-    // shuffle under the && of the comparison runs only in the lanes whose low
-    // halves matched, and reads 0 from a neighbour that is not among them --
-    // equal to the high half of a small key.
+    // (both halves shuffled before either is compared: lane_runs' rule)
     const uint32_t k_lo = (uint32_t)key, k_hi = (uint32_t)(key >> 32);
     const uint32_t below_lo = __shfl_up(k_lo, 1), below_hi = __shfl_up(k_hi, 1);
-    const bool same = below_lo == k_lo && below_hi == k_hi;
-    const bool head = keyed && (lane == 0u || !same);
-    const uint64_t heads = __ballot(head);
-    // the last head at or below this lane (32-bit shifts only)
-    const uint32_t m_lo = lane < 32u ? (2u << lane) - 1u : 0xFFFFFFFFu;
-    const uint32_t m_hi = lane < 32u ? 0u : (2u << (lane - 32u)) - 1u;
-    const uint32_t h_lo = (uint32_t)heads & m_lo, h_hi = (uint32_t)(heads >> 32) & m_hi;
-    const uint32_t first = h_hi ? 63u - (uint32_t)__builtin_clz(h_hi)
-                                : (h_lo ? 31u - (uint32_t)__builtin_clz(h_lo) : 0u);
+    const LaneRun run = lane_runs(keyed, below_lo == k_lo && below_hi == k_hi, lane);
     uint32_t e = kAssignNone;
-    if (head) {
+    if (run.head) {
       e = assign_find_or_claim(a, key);
       if (e <= a.cap_mask) {
         // (the value is final since the slots pass: this kernel never writes it)
@@ -1673,7 +1712,7 @@ __global__ __launch_bounds__(kReviveTile) void assign_probe_kernel(AssignArgs a)
         atomicOr(a.err, kErrMissingIndex);
       }
     }
-    e = __shfl(e, first);  // (a keyed lane's run has a head: itself or one below it)
+    e = __shfl(e, run.first);  // (a keyed lane's run has a head: itself or one below it)
     if (in) a.ent[p] = keyed ? e : kAssignNone;
   }
 }
@@ -1686,55 +1725,24 @@ __device__ __forceinline__ bool assign_opener(const AssignArgs& a, uint64_t p, u
 }
 
 __global__ __launch_bounds__(kReviveTile) void assign_tile_kernel(AssignArgs a) {
-  __shared__ uint32_t s_w[kReviveTile / 64];
+  __shared__ uint32_t s_w[kTurnWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint64_t ntile = (a.n_packets + kReviveTile - 1) / kReviveTile;
   for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     uint32_t e;
-    const uint32_t c = (uint32_t)__popcll(__ballot(assign_opener(a, tile * kReviveTile + tid, e)));
-    if (lane == 0u) s_w[wave] = c;
-    __syncthreads();
-    if (tid == 0u) a.open_tile[tile] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();  // s_w is reused by the next tile
+    const uint32_t opening =
+        (uint32_t)__popcll(__ballot(assign_opener(a, tile * kReviveTile + tid, e)));
+    const uint32_t t = block_sum(opening, lane, wave, s_w);
+    if (tid == 0u) a.open_tile[tile] = t;
   }
-}
-
-// v[i] = the sum of v[0..i) in place over n words, by one workgroup of
-// kRvScanBlock lanes (every lane reads its own word before it writes it);
-// returns the sum of all.  Sums fit 32 bits: they count packets or slots.
-__device__ __forceinline__ uint32_t assign_scan_in_place(uint32_t* v, uint64_t n, uint32_t* s_sum) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  uint32_t base = 0;
-  for (uint64_t t0 = 0; t0 < n; t0 += kRvScanBlock) {
-    const uint64_t i = t0 + tid;
-    const uint32_t c = i < n ? v[i] : 0u;
-    uint32_t x = c;  // inclusive scan within the wave
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t y = __shfl_up(x, d);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63u) s_sum[wave] = x;
-    __syncthreads();
-    uint32_t before = 0, tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kRvScanBlock / 64; ++w) {
-      if (w < wave) before += s_sum[w];
-      tot += s_sum[w];
-    }
-    if (i < n) v[i] = base + before + (x - c);
-    base += tot;
-    __syncthreads();
-  }
-  return base;
 }
 
 __global__ __launch_bounds__(kRvScanBlock) void assign_scan_kernel(AssignArgs a) {
-  __shared__ uint32_t s_sum[kRvScanBlock / 64];
-  const uint32_t n_free = assign_scan_in_place(
-      a.free_tile, ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile, s_sum);
-  const uint32_t n_open = assign_scan_in_place(
-      a.open_tile, (a.n_packets + kReviveTile - 1) / kReviveTile, s_sum);
+  __shared__ uint32_t s_w[kRvScanBlock / 64];
+  const uint32_t n_free = tile_scan_in_place(
+      a.free_tile, ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile, s_w);
+  const uint32_t n_open = tile_scan_in_place(
+      a.open_tile, (a.n_packets + kReviveTile - 1) / kReviveTile, s_w);
   if (threadIdx.x == 0u) {
     a.totals[0] = n_free;
     if (a.counts) a.counts[3] = min(n_free, n_open);  // (zeroed by the slots pass)
@@ -1742,30 +1750,22 @@ __global__ __launch_bounds__(kRvScanBlock) void assign_scan_kernel(AssignArgs a)
 }
 
 __global__ __launch_bounds__(kReviveTile) void assign_free_kernel(AssignArgs a) {
-  __shared__ uint32_t s_w[kReviveTile / 64];
+  __shared__ uint32_t s_w[kTurnWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
   for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     const uint64_t s = tile * kReviveTile + tid;
     const bool in = s < a.n_slots;
     const bool is_free = in && a.acc_len[in ? s : a.n_slots - 1u] == 0;
-    const uint64_t b = __ballot(is_free);
-    if (lane == 0u) s_w[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    // the free slots of the lanes below this one
-    const uint32_t b_lo = (uint32_t)b, b_hi = (uint32_t)(b >> 32);
-    uint32_t pos = lane < 32u ? (uint32_t)__popc(b_lo & ((1u << lane) - 1u))
-                              : (uint32_t)__popc(b_lo) +
-                                    (uint32_t)__popc(b_hi & ((1u << (lane - 32u)) - 1u));
-    for (uint32_t w = 0; w < wave; ++w) pos += s_w[w];
-    const uint64_t r = (uint64_t)a.free_tile[tile] + pos;
+    // the free slots of the tiles and of the tile's lanes below this one
+    const uint64_t r =
+        (uint64_t)a.free_tile[tile] + block_ballot_rank(__ballot(is_free), lane, wave, s_w);
     if (is_free && r < a.n_slots) a.free_list[r] = (uint32_t)s;
-    __syncthreads();  // s_w is reused by the next tile
   }
 }
 
 __global__ __launch_bounds__(kReviveTile) void assign_open_kernel(AssignArgs a) {
-  __shared__ uint32_t s_w[kReviveTile / 64];
+  __shared__ uint32_t s_w[kTurnWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint64_t ntile = (a.n_packets + kReviveTile - 1) / kReviveTile;
   const uint32_t n_free = min(a.totals[0], a.n_slots);
@@ -1773,15 +1773,9 @@ __global__ __launch_bounds__(kReviveTile) void assign_open_kernel(AssignArgs a) 
     const uint64_t p = tile * kReviveTile + tid;
     uint32_t e;
     const bool opener = assign_opener(a, p, e);
-    const uint64_t b = __ballot(opener);
-    if (lane == 0u) s_w[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    const uint32_t b_lo = (uint32_t)b, b_hi = (uint32_t)(b >> 32);
-    uint32_t pos = lane < 32u ? (uint32_t)__popc(b_lo & ((1u << lane) - 1u))
-                              : (uint32_t)__popc(b_lo) +
-                                    (uint32_t)__popc(b_hi & ((1u << (lane - 32u)) - 1u));
-    for (uint32_t w = 0; w < wave; ++w) pos += s_w[w];
-    const uint64_t r = (uint64_t)a.open_tile[tile] + pos;  // its rank among the openers, by p
+    // its rank among the openers, by p
+    const uint64_t r =
+        (uint64_t)a.open_tile[tile] + block_ballot_rank(__ballot(opener), lane, wave, s_w);
     if (opener && r < n_free) {
       const uint32_t s = a.free_list[r];
       if (s < a.n_slots) {
@@ -1790,14 +1784,14 @@ __global__ __launch_bounds__(kReviveTile) void assign_open_kernel(AssignArgs a) 
         a.slot_k[s] = a.pkt_k[p];
       }
     }
-    __syncthreads();  // s_w is reused by the next tile
   }
 }
 
 __global__ __launch_bounds__(kReviveTile) void assign_emit_kernel(AssignArgs a) {
-  __shared__ uint32_t s_w[kReviveTile / 64][4];
+  __shared__ uint32_t s_w[kTurnWaves * 4];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  uint32_t n_old = 0, n_new = 0, n_none = 0, n_away = 0;  // the wave's (uniform)
+  // the wave's packets (uniform): to an open group, to a new one, keyless, turned away
+  uint32_t n[4] = {0, 0, 0, 0};
   const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
   for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
     const uint64_t p = p0 + tid;
@@ -1815,25 +1809,16 @@ __global__ __launch_bounds__(kReviveTile) void assign_emit_kernel(AssignArgs a) 
     }
     const bool placed = s < a.n_slots;
     if (in) a.pkt_slot_out[p] = placed ? s : kAssignNone;
-    n_old += (uint32_t)__popcll(__ballot(placed && !opened));
-    n_new += (uint32_t)__popcll(__ballot(placed && opened));
-    n_none += (uint32_t)__popcll(__ballot(in && !keyed));
-    n_away += (uint32_t)__popcll(__ballot(keyed && !placed));
+    n[0] += (uint32_t)__popcll(__ballot(placed && !opened));
+    n[1] += (uint32_t)__popcll(__ballot(placed && opened));
+    n[2] += (uint32_t)__popcll(__ballot(in && !keyed));
+    n[3] += (uint32_t)__popcll(__ballot(keyed && !placed));
   }
-  if (lane == 0u) {
-    s_w[wave][0] = n_old;
-    s_w[wave][1] = n_new;
-    s_w[wave][2] = n_none;
-    s_w[wave][3] = n_away;
-  }
-  __syncthreads();
-  if (tid < 4u && a.counts) {
-    const uint32_t t = s_w[0][tid] + s_w[1][tid] + s_w[2][tid] + s_w[3][tid];
-    // counts[0..2] and counts[4]; counts[3] is the scan's
-    if (t != 0u) atomicAdd(&a.counts[tid < 3u ? tid : 4u], (unsigned long long)t);
-  }
+  const uint32_t t = block_sum(n, lane, wave, s_w);
+  // counts[0..2] and counts[4]; counts[3] is the scan's
+  if (tid < 4u && a.counts && t != 0u)
+    atomicAdd(&a.counts[tid < 3u ? tid : 4u], (unsigned long long)t);
 }
-static_assert(kReviveTile == 256, "four waves' counts are summed by hand above");
 
 // The recover body over the work list, L >= 16: lanes, windows and loads as
 // fixed_xor_kernel; workgroup step i takes entries [i * gpb, (i + 1) * gpb).
@@ -1997,10 +1982,6 @@ constexpr int kRaggedU = 2;     // flat-window loops: iterations' loads in fligh
 constexpr int kWindowPB = 16;   // ragged_window_kernel: load slots per trip
 constexpr int kParWin = 92;  // ceil(1452/16) = 91 windows (+1 spare)
 
-__device__ __forceinline__ uint32_t lane_id() {
-  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
-
 // The group's LDS state (accumulator, start mask, packet table) passes data
 // between lanes of one wave.  The LDS executes a wave's accesses in program
 // order; wavefront-scope fences around a wave barrier keep the compiler from
@@ -2011,24 +1992,8 @@ __device__ __forceinline__ void wave_lds_order() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Lane src's x (ds_bpermute; src in [0, 64)).  The shuffles below take the
-// caller's lane instead of HIP's __shfl*, which recompute it (mbcnt) and
-// whose lane-derived addresses the compiler hoists out of a resident loop:
-// in the service worker they stayed live through the whole job body and
-// spilled to scratch at 256 VGPRs (round 6).
-__device__ __forceinline__ uint32_t lane_read(uint32_t x, uint32_t src) {
-  return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)x);
-}
-
-// Inclusive prefix sum over the wave.
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = lane_read(x, lane >= (uint32_t)d ? lane - (uint32_t)d : lane);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  return x;
-}
+// (lane_id, lane_read, wave_incl_scan and block_excl_scan: the workgroup
+// primitives above the revive passes)
 
 // The accumulator is only ever accessed as uint32_t (plain and atomic): one
 // type, so the compiler cannot reorder the plain initialisation / final reads
@@ -2391,24 +2356,7 @@ constexpr uint32_t kAccWords = 4 * kParWin;
 // run the per-group body, one wave per group, so outputs and error bits are
 // exactly those of the per-group kernel.  Encode parity lengths come from an
 // LDS atomicMax.
-template <int WAVES>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t lane, uint32_t wv,
-                                                    uint32_t* s_w, uint32_t& total) {
-  const uint32_t incl = wave_incl_scan(x, lane);
-  if (lane == 63u) s_w[wv] = incl;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < WAVES; ++w) {
-    const uint32_t v = s_w[w];
-    base += (uint32_t)w < wv ? v : 0u;
-    tot += v;
-  }
-  total = tot;
-  __syncthreads();  // s_w free again
-  return base + incl - x;
-}
-
+//
 // Recover and accumulate load their rows' windows into the accumulators before
 // the packet table, so their round trip overlaps the table's; kRaggedU
 // iterations' loads are in flight; a last window whose start is 16-B aligned
@@ -4143,21 +4091,36 @@ hipError_t launch_revive_k(const ReviveArgs& a, uint32_t C, uint32_t gpb, uint32
   return hipGetLastError();
 }
 
+// The grids of the turn passes, in workgroups of kReviveTile lanes that loop.
+// Per tile, where a workgroup scans or ranks a tile of n elements at a time:
+inline uint32_t tile_grid(uint64_t n) {
+  return (uint32_t)std::min<uint64_t>(revive_tiles(n), kMaxBlocks256);
+}
+// per packet, where it keeps tallies or only streams: sixteen per CU, so that
+// the tallies cost a few atomics per workgroup and not per 256 packets
+inline uint32_t per_packet_grid(uint64_t n, uint32_t ncu) {
+  return (uint32_t)std::min<uint64_t>(revive_tiles(n), (uint64_t)(ncu ? ncu : 256u) * 16u);
+}
+
+// One kernel of a call's chain, launched on s unless a launch before it failed
+// (e, what the launch before returned); returns the chain's first failure.
+template <typename Args>
+hipError_t launch_pass(hipError_t e, void (*kernel)(Args), uint32_t grid, uint32_t block,
+                       hipStream_t s, const Args& a) {
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, a);
+  return hipGetLastError();
+}
+
 // The first three launches of every revive (classify, scan, emit), for any of
-// the revive argument structs.  classify and emit: grid-stride over the tiles
-// of kReviveTile groups.
+// the revive argument structs.
 template <typename Args>
 hipError_t launch_revive_passes(const Args& a, hipStream_t s) {
-  const uint32_t cgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
-  hipLaunchKernelGGL((revive_classify_kernel<false, Args>), dim3(cgrid), dim3(kReviveTile), 0, s,
-                     a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(revive_scan_kernel<Args>, dim3(1), dim3(kRvScanBlock), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL((revive_classify_kernel<true, Args>), dim3(cgrid), dim3(kReviveTile), 0, s,
-                     a);
-  return hipGetLastError();
+  hipError_t e = launch_pass(hipSuccess, revive_classify_kernel<false, Args>,
+                             tile_grid(a.n_groups), kReviveTile, s, a);
+  e = launch_pass(e, revive_scan_kernel<Args>, 1, kRvScanBlock, s, a);
+  e = launch_pass(e, revive_classify_kernel<true, Args>, tile_grid(a.n_groups), kReviveTile, s, a);
+  return e;
 }
 
 }  // namespace
@@ -4253,65 +4216,39 @@ hipError_t launch_tracked_revive(const TrackedCloseArgs& a, hipStream_t s) {
 
 hipError_t launch_admit_ragged(const AdmitArgs& a, hipStream_t s) {
   if (a.n_groups == 0) return hipSuccess;
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_groups), kMaxBlocks256);
-  hipLaunchKernelGGL(admit_decide_kernel, dim3(grid), dim3(kReviveTile), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(admit_scan_kernel, dim3(1), dim3(kRvScanBlock), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(admit_scatter_kernel, dim3(grid), dim3(kReviveTile), 0, s, a);
-  return hipGetLastError();
+  hipError_t e = launch_pass(hipSuccess, admit_decide_kernel, tile_grid(a.n_groups), kReviveTile, s, a);
+  e = launch_pass(e, admit_scan_kernel, 1, kRvScanBlock, s, a);
+  e = launch_pass(e, admit_scatter_kernel, tile_grid(a.n_groups), kReviveTile, s, a);
+  return e;
 }
 
 hipError_t launch_bin_arrivals(const BinArgs& a, hipStream_t s) {
   if (a.n_packets == 0 || a.n_slots == 0) return hipSuccess;
   hipError_t e = hipMemsetAsync(a.tally, 0, bin_scratch_zeroed(a.n_slots), s);
-  if (e != hipSuccess) return e;
-  // per packet: the workgroups loop, sixteen per CU, so that the tallies cost
-  // three atomics per workgroup and not per 256 packets
-  const uint32_t pgrid = (uint32_t)std::min<uint64_t>(
-      (a.n_packets + kReviveTile - 1) / kReviveTile, (uint64_t)(a.ncu ? a.ncu : 256u) * 16u);
-  const uint32_t sgrid = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_slots), kMaxBlocks256);
-  hipLaunchKernelGGL(bin_count_kernel, dim3(pgrid), dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(bin_tile_kernel, dim3(sgrid), dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(kRvScanBlock), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(bin_ptr_kernel, dim3(sgrid), dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(bin_scatter_kernel, dim3(pgrid), dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(bin_order_kernel, dim3(sgrid), dim3(kReviveTile), 0, s, a);
-  return hipGetLastError();
+  const uint32_t pgrid = per_packet_grid(a.n_packets, a.ncu), sgrid = tile_grid(a.n_slots);
+  e = launch_pass(e, bin_count_kernel, pgrid, kReviveTile, s, a);
+  e = launch_pass(e, bin_tile_kernel, sgrid, kReviveTile, s, a);
+  e = launch_pass(e, bin_scan_kernel, 1, kRvScanBlock, s, a);
+  e = launch_pass(e, bin_ptr_kernel, sgrid, kReviveTile, s, a);
+  e = launch_pass(e, bin_scatter_kernel, pgrid, kReviveTile, s, a);
+  e = launch_pass(e, bin_order_kernel, sgrid, kReviveTile, s, a);
+  return e;
 }
 
 hipError_t launch_assign_slots(const AssignArgs& a, hipStream_t s) {
   if (a.n_packets == 0) return hipSuccess;
   hipError_t e = hipMemsetAsync(a.table, 0xFF, ((uint64_t)a.cap_mask + 1u) * 16u, s);
-  if (e != hipSuccess) return e;
-  // per packet where a workgroup keeps tallies or only streams: the workgroups
-  // loop, sixteen per CU, as in launch_bin_arrivals; per tile where it scans
-  const uint32_t pgrid = (uint32_t)std::min<uint64_t>(
-      revive_tiles(a.n_packets), (uint64_t)(a.ncu ? a.ncu : 256u) * 16u);
-  const uint32_t ptiles = (uint32_t)std::min<uint64_t>(revive_tiles(a.n_packets), kMaxBlocks256);
+  const uint32_t pgrid = per_packet_grid(a.n_packets, a.ncu), ptiles = tile_grid(a.n_packets);
   // (no slots: one workgroup still zeroes counts)
-  const uint32_t stiles = (uint32_t)std::min<uint64_t>(
-      std::max<uint64_t>(revive_tiles(a.n_slots), 1), kMaxBlocks256);
-  hipLaunchKernelGGL(assign_slots_kernel, dim3(stiles), dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(assign_probe_kernel, dim3(pgrid), dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(assign_tile_kernel, dim3(ptiles), dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(assign_scan_kernel, dim3(1), dim3(kRvScanBlock), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(assign_free_kernel, dim3(stiles), dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(assign_open_kernel, dim3(ptiles), dim3(kReviveTile), 0, s, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(assign_emit_kernel, dim3(pgrid), dim3(kReviveTile), 0, s, a);
-  return hipGetLastError();
+  const uint32_t stiles = std::max(tile_grid(a.n_slots), 1u);
+  e = launch_pass(e, assign_slots_kernel, stiles, kReviveTile, s, a);
+  e = launch_pass(e, assign_probe_kernel, pgrid, kReviveTile, s, a);
+  e = launch_pass(e, assign_tile_kernel, ptiles, kReviveTile, s, a);
+  e = launch_pass(e, assign_scan_kernel, 1, kRvScanBlock, s, a);
+  e = launch_pass(e, assign_free_kernel, stiles, kReviveTile, s, a);
+  e = launch_pass(e, assign_open_kernel, ptiles, kReviveTile, s, a);
+  e = launch_pass(e, assign_emit_kernel, pgrid, kReviveTile, s, a);
+  return e;
 }
 
 hipError_t launch_accumulate_ragged(const AccumulateRaggedArgs& a0, hipStream_t s) {
