@@ -37,6 +37,11 @@
  *       the packet's group and a new group inserted when there is none
  *       (quic_connection.cc:1388-1392), for a whole turn: per-packet 64-bit
  *       group keys become the per-packet slots the bin reads.
+ *   qfec_retire_groups
+ *       is what bounds that map: QuicFecReceiver::CloseFecGroupsBefore (a
+ *       STOP_WAITING's threshold drops every group waiting for a packet below
+ *       it, for good) and GetFecGroup's kMaxFecGroups eviction, for a whole
+ *       turn in front of the assign: per-connection watermarks.
  *   qfec_recover_batch / _strided / qfec_recover_ragged
  *       replaces QuicFecGroup::UpdateFec + Update(received) + CanRevive() +
  *       Revive().  Receive-side hook: QuicConnection::ProcessValidatedPacket
@@ -733,10 +738,12 @@ int qfec_bin_arrivals(qfec_ctx* ctx, const uint32_t* pkt_slot, const uint64_t* p
  * If every candidate of a new group fails its tag nothing was folded, and the
  * slot is free again with nothing lost.
  * What stays with the host: the key and the position (pkt_idx) from the
- * cleartext header; the policy, expressed through QFEC_NO_KEY -- which packets
- * are candidates at all, and a per-connection watermark below which a closed
- * group is never reopened (a late duplicate of a released group would open it
- * anew under its key); and forced closes, for which it reads slot_key back.
+ * cleartext header, and which packets are candidates at all, expressed through
+ * QFEC_NO_KEY.  A late duplicate of a released group would open it anew under
+ * its key: the per-connection watermark below which a group is never reopened,
+ * the forced closes and the bound on a connection's open groups are
+ * qfec_retire_groups' (below), which runs in front of this call and hands it
+ * the keys it passes.
  * Refused on the host (nothing launched, nothing written): QFEC_PTR_HOST,
  * QFEC_PTR_MAPPED or QFEC_ASYNC; a NULL buffer other than counts; n_packets >=
  * 2^32 or n_slots >= 2^32, or more than 2^30 of both together
@@ -756,6 +763,92 @@ int qfec_assign_slots(qfec_ctx* ctx, const uint64_t* pkt_key, const uint8_t* pkt
                       uint64_t n_packets, uint64_t* slot_key, uint8_t* slot_k,
                       const uint16_t* acc_len, uint64_t n_slots, uint32_t* pkt_slot_out,
                       uint64_t* counts, uint32_t flags);
+
+/* Group retention and forced closes on the device: the other half of the
+ * connection's group map.  QuicFecReceiver::CloseFecGroupsBefore drops every
+ * group below a STOP_WAITING's threshold and never recreates it; GetFecGroup,
+ * with kMaxFecGroups groups open on a connection, drops the lowest and refuses
+ * a group older than all it keeps.  This call applies both to a whole turn, in
+ * front of the assign: the turn is open -> qfec_retire_groups ->
+ * qfec_assign_slots -> qfec_bin_arrivals -> qfec_admit_ragged ->
+ * qfec_accumulate_ragged -> qfec_revive_tracked on one stream, with no sync and
+ * no host decision in between.  Per packet the host supplies what the header
+ * gives, per connection only the STOP_WAITING thresholds of the turn.
+ *
+ * This is the only call that interprets a key.  A key other than QFEC_NO_KEY
+ * reads conn = key >> key_shift and number = key & ((1 << key_shift) - 1),
+ * key_shift in 1..63 (connection index << 40 | group number: key_shift = 40).
+ * conn_mark[c] is connection c's watermark: a group of c with number <
+ * conn_mark[c] is dead; a mark of 0 kills nothing.  A group's number being its
+ * first protected packet number, number < mark is
+ * QuicFecGroup::IsWaitingForPacketBefore(mark).
+ * The rule, stated sequentially; the outputs are exactly these, a pure function
+ * of the inputs (no scheduling, atomic order or hash shows in them):
+ *   1 raise: for i in 0 .. n_raise - 1, conn_mark[raise_conn[i]] = max(itself,
+ *     raise_mark[i]) -- the turn's STOP_WAITING thresholds.  A connection may
+ *     appear several times; a threshold below the mark changes nothing;
+ *     n_raise == 0 with NULL tables is allowed.
+ *   2 retain, only with max_groups > 0: for every connection c let L_c be the
+ *     DISTINCT numbers >= conn_mark[c] among the open keyed slots of c
+ *     (acc_len[s] > 0 and slot_key[s] != QFEC_NO_KEY; a free slot's stale key
+ *     does not count) and the call's keyed packets of c.  If |L_c| >
+ *     max_groups, conn_mark[c] becomes the max_groups-th largest element of
+ *     L_c: the map holds the max_groups highest groups seen, and everything
+ *     below the lowest kept one is refused.  max_groups == 0: no bound.
+ *   3 close: every open keyed slot with number < conn_mark[conn] gets
+ *     acc_len[s] = 0 and is listed, in ascending s, in closed_list (may be
+ *     NULL; else room for n_slots entries; entries from the count on are not
+ *     written).  Two open slots under one key are both closed.  slot_key,
+ *     slot_k, the maps and the rows are never written: the slot is free by the
+ *     fresh-slot rule, as after any other close, and slot_key[closed_list[i]]
+ *     still names the group that went.
+ *   4 filter: pkt_key_out[p] = QFEC_NO_KEY if pkt_key[p] is QFEC_NO_KEY or its
+ *     number is below its connection's mark, else pkt_key[p].  pkt_key_out ==
+ *     pkt_key (in place) is allowed.  The assign then reads pkt_key_out.
+ * counts[0..4] (may be NULL): slots closed; packets refused, below their mark;
+ * packets that came in as QFEC_NO_KEY; packets passed; keys (of packets and of
+ * open slots) and raises with a connection out of range.  The first four are
+ * results, and every packet is counted in exactly one of [1], [2], [3], [4].
+ * Connection out of range (conn >= n_conns): such a packet's key goes out as
+ * QFEC_NO_KEY and it takes no part in step 2; such an open slot is left alone;
+ * such a raise is skipped.  Each is latched on the device and returned by the
+ * next qfec_sync as -QUIC_INVALID_FEC_DATA; every other output is right.  An
+ * open slot holding QFEC_NO_KEY (a group the host opened itself) takes part in
+ * nothing.
+ * Ordering: the retire runs before the assign of the same turn on the same
+ * stream.  The assign sees the slots closed here as free and reuses them with
+ * nothing cleared; between the two the host does nothing.
+ * What stays with the host: the key and the position from the cleartext
+ * header; which packets are candidates at all; and raising a mark past a group
+ * that finished or was revived ahead of older open ones, for which it has
+ * revived_list and status and feeds the raise list.
+ * Where the turn differs from the per-packet reference: packets of a group
+ * evicted later in the same turn are not folded first (the reference would
+ * have folded them, and might have revived the group before evicting it); and
+ * the mark is monotone (after a kept group finishes, the reference would again
+ * create a never-seen group below the lowest kept one; the mark refuses it).
+ * Refused on the host (nothing launched, nothing written): QFEC_PTR_HOST,
+ * QFEC_PTR_MAPPED or QFEC_ASYNC; NULL slot_key or acc_len with n_slots > 0;
+ * NULL pkt_key or pkt_key_out with n_packets > 0; NULL conn_mark with n_conns >
+ * 0; NULL raise tables with n_raise > 0; key_shift outside 1..63; max_groups >
+ * 16; n_packets, n_slots, n_conns or n_raise >= 2^32 (QFEC_ERR_INTERNAL, in
+ * that order).  n_packets == 0 with slots present is an ordinary call, the
+ * pure CloseFecGroupsBefore, and n_slots == 0 with packets present is one too;
+ * only when n_packets, n_slots and n_raise are all 0 does the call succeed
+ * before the buffers are looked at (counts, if given, receives five zeroes).
+ * QFEC_CACHED and QFEC_SMALL_GROUPS are accepted and change nothing.  Device
+ * pointers only; the call only queues work on the context's stream, never
+ * waits and never reads anything back.  Its intermediate state lives in the
+ * context-owned scratch of qfec_revive_batch and is rebuilt by every call: 64
+ * bytes, 4 bytes per 256 slots and, with max_groups > 0, 8 * (max_groups + 1)
+ * bytes per connection; nothing per packet.  The calls that follow on the same
+ * stream reuse the block; stream order makes that safe. */
+int qfec_retire_groups(qfec_ctx* ctx, const uint64_t* pkt_key, uint64_t n_packets,
+                       const uint64_t* slot_key, uint16_t* acc_len, uint64_t n_slots,
+                       uint64_t* conn_mark, uint64_t n_conns, uint32_t key_shift,
+                       uint32_t max_groups, const uint32_t* raise_conn,
+                       const uint64_t* raise_mark, uint64_t n_raise, uint64_t* pkt_key_out,
+                       uint32_t* closed_list, uint64_t* counts, uint32_t flags);
 
 /* ---- single buffer ------------------------------------------------------ */
 /* out[j] ^= in[j] for j < n (QuicFecGroupInterface::XorBuffers). */

@@ -2448,6 +2448,63 @@ int qfec_assign_slots(qfec_ctx* ctx, const uint64_t* pkt_key, const uint8_t* pkt
   return revive_scratch_release(ctx);
 }
 
+// QuicFecReceiver::CloseFecGroupsBefore and the kMaxFecGroups eviction of
+// QuicConnection::GetFecGroup, for a whole turn in front of the assign: the
+// per-connection watermarks raised, the max_groups highest groups kept, the
+// open slots below their mark closed and the packets below it masked.  One
+// memset and at most max_groups + 7 kernels on the stream, in the revive
+// calls' scratch; every check that needs the tables is the kernels'.
+int qfec_retire_groups(qfec_ctx* ctx, const uint64_t* pkt_key, uint64_t n_packets,
+                       const uint64_t* slot_key, uint16_t* acc_len, uint64_t n_slots,
+                       uint64_t* conn_mark, uint64_t n_conns, uint32_t key_shift,
+                       uint32_t max_groups, const uint32_t* raise_conn,
+                       const uint64_t* raise_mark, uint64_t n_raise, uint64_t* pkt_key_out,
+                       uint32_t* closed_list, uint64_t* counts, uint32_t flags) {
+  const char* const what = "retire groups";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_device_only(ctx, what, flags))) return rc;
+  if (n_packets == 0 && n_slots == 0 && n_raise == 0) return zero_counts(ctx, counts, 5);
+  if ((n_slots != 0 && (!slot_key || !acc_len)) || (n_packets != 0 && (!pkt_key || !pkt_key_out)) ||
+      (n_conns != 0 && !conn_mark) || (n_raise != 0 && (!raise_conn || !raise_mark)))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: null buffer (only closed_list and counts may be NULL, and the tables of "
+                "a count that is 0)", what);
+  if (key_shift < 1 || key_shift > 63)
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: key_shift %u outside [1, 63]", what, key_shift);
+  if (max_groups > qfec::kRetireMaxGroups)
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: max_groups %u above %u", what, max_groups,
+                qfec::kRetireMaxGroups);
+  if (n_packets >= (1ull << 32) || n_slots >= (1ull << 32) || n_conns >= (1ull << 32) ||
+      n_raise >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: 2^32 or more packets, slots, connections or raises (their indices are 32 "
+                "bits)", what);
+  if ((rc = revive_scratch_acquire_bytes(
+           ctx, qfec::retire_scratch_bytes(n_conns, n_slots, max_groups))))
+    return rc;
+  qfec::RetireArgs a{};
+  a.pkt_key = reinterpret_cast<const unsigned long long*>(pkt_key);
+  a.n_packets = n_packets;
+  a.slot_key = reinterpret_cast<const unsigned long long*>(slot_key);
+  a.acc_len = acc_len;
+  a.n_slots = (uint32_t)n_slots;
+  a.conn_mark = reinterpret_cast<unsigned long long*>(conn_mark);
+  a.n_conns = (uint32_t)n_conns;
+  a.key_shift = key_shift;
+  a.max_groups = max_groups;
+  a.raise_conn = raise_conn;
+  a.raise_mark = reinterpret_cast<const unsigned long long*>(raise_mark);
+  a.n_raise = (uint32_t)n_raise;
+  a.pkt_key_out = reinterpret_cast<unsigned long long*>(pkt_key_out);
+  a.closed_list = closed_list;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.err = ctx->d_err;
+  a.ncu = ctx->ncu;
+  qfec::retire_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_retire_groups(a, ctx->stream));
+  return revive_scratch_release(ctx);
+}
+
 // qfec_revive_accumulated with the group's K and map kept per slot, where
 // qfec_admit_ragged maintains them.
 int qfec_revive_tracked(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride, uint16_t* acc_len,

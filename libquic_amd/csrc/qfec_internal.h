@@ -412,6 +412,57 @@ inline void assign_scratch_layout(AssignArgs& a, void* block) {
 // emit), ordered by the stream alone.  n_packets > 0.
 hipError_t launch_assign_slots(const AssignArgs& a, hipStream_t s);
 
+// qfec_retire_groups: per-connection watermarks raised, the max_groups highest
+// groups of every connection kept, the open slots below their mark closed and
+// the packets below it masked, in front of the assign (rule as include/qfec.h).
+// Scratch, a block of retire_scratch_bytes(n_conns, n_slots, max_groups) in the
+// revive calls' allocation: eight tallies and, with max_groups > 0, max_groups
+// + 1 words per connection (round r's word: the r-th largest live number + 1,
+// 0 = none), zeroed together in front of the kernels; a word per tile of
+// kReviveTile slots.
+constexpr uint32_t kRetireMaxGroups = 16;
+constexpr uint64_t kRetireTallyBytes = 64;
+struct RetireArgs {
+  const unsigned long long* pkt_key;  // nullable with n_packets == 0
+  uint64_t n_packets;                 // < 2^32
+  const unsigned long long* slot_key;
+  uint16_t* acc_len;
+  uint32_t n_slots;  // may be 0
+  unsigned long long* conn_mark;
+  uint32_t n_conns;     // may be 0: every key is out of range
+  uint32_t key_shift;   // 1..63
+  uint32_t max_groups;  // <= kRetireMaxGroups; 0: no bound
+  uint32_t round;       // the retain pass this launch runs, 0 .. max_groups
+  const uint32_t* raise_conn;
+  const unsigned long long* raise_mark;
+  uint32_t n_raise;
+  unsigned long long* pkt_key_out;  // may be pkt_key
+  uint32_t* closed_list;            // nullable
+  unsigned long long* counts;  // nullable: [closed, refused, no key, passed, out of range]
+  unsigned long long* tally;   // scratch: 8, [1..4] as counts
+  unsigned long long* top;     // scratch: (max_groups + 1) * n_conns, round-major
+  uint32_t* tile_off;          // scratch: 1 per tile of slots
+  uint32_t* err;
+  uint32_t ncu;
+};
+// the tallies and the round words: what the memset in front of the kernels clears
+inline uint64_t retire_scratch_zeroed(uint64_t n_conns, uint32_t max_groups) {
+  return kRetireTallyBytes + (max_groups ? (uint64_t)(max_groups + 1) * n_conns * 8 : 0);
+}
+inline uint64_t retire_scratch_bytes(uint64_t n_conns, uint64_t n_slots, uint32_t max_groups) {
+  return retire_scratch_zeroed(n_conns, max_groups) + revive_tiles(n_slots) * 4;
+}
+inline void retire_scratch_layout(RetireArgs& a, void* block) {
+  uint8_t* p = static_cast<uint8_t*>(block);
+  a.tally = reinterpret_cast<unsigned long long*>(p);
+  a.top = reinterpret_cast<unsigned long long*>(p + kRetireTallyBytes);
+  a.tile_off = reinterpret_cast<uint32_t*>(p + retire_scratch_zeroed(a.n_conns, a.max_groups));
+}
+// One memset and up to max_groups + 7 launches on s (raise, the retain rounds,
+// mark, filter, classify, scan, close), ordered by the stream alone.  Not all
+// of n_packets, n_slots and n_raise are 0.
+hipError_t launch_retire_groups(const RetireArgs& a, hipStream_t s);
+
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch
 // per batch (the launch is most of a small flush's connection-thread cost).

@@ -1820,6 +1820,222 @@ __global__ __launch_bounds__(kReviveTile) void assign_emit_kernel(AssignArgs a) 
     atomicAdd(&a.counts[tid < 3u ? tid : 4u], (unsigned long long)t);
 }
 
+// ---------------------------------------------------------------------------
+// Group retention and forced closes (qfec_retire_groups): the watermark of
+// QuicFecReceiver::CloseFecGroupsBefore and the kMaxFecGroups eviction of
+// GetFecGroup, in front of the assign.
+// ---------------------------------------------------------------------------
+// The one call that reads a key: conn = key >> key_shift, number = the bits
+// below.  Behind one memset of the tallies and the round words:
+//   raise    : one lane per raise, a 64-bit atomicMax into conn_mark;
+//   round r  : (max_groups + 1 of them, only with max_groups > 0) one lane per
+//              slot, then per packet; a live number (at or above its mark)
+//              below round r - 1's result goes by atomicMax, as number + 1,
+//              into the connection's word of round r: the r-th largest
+//              distinct live number, 0 if there is none.  One atomic per run of
+//              neighbouring lanes with one key, and none where the word
+//              already holds as much;
+//   mark     : one lane per connection; where round max_groups found a
+//              number, more than max_groups are live and conn_mark becomes
+//              round max_groups - 1's, the max_groups-th largest;
+//   filter   : one lane per packet, pkt_key_out and the four packet tallies;
+//   classify : one lane per slot, the slots to close counted per tile;
+//   scan     : one workgroup, an exclusive scan over the tile counts, counts;
+//   close    : the classification again, acc_len = 0 and closed_list at the
+//              scanned position: ascending, no sort.
+// A maximum does not depend on the order of its operands, so the atomics show
+// nowhere.  Every connection index is checked against n_conns before it
+// indexes conn_mark or a round word, every place in closed_list against
+// n_slots.  All variable shifts are 32-bit (the gfx950 64-bit shift hazard).
+__device__ __forceinline__ bool retire_split(const RetireArgs& a, unsigned long long key,
+                                             uint32_t& conn, unsigned long long& number) {
+  const uint32_t lo = (uint32_t)key, hi = (uint32_t)(key >> 32), sh = a.key_shift;
+  uint32_t c_lo, c_hi, n_lo, n_hi;
+  if (sh >= 32u) {
+    const uint32_t t = sh - 32u;  // 0 .. 31
+    c_lo = hi >> t;
+    c_hi = 0u;
+    n_lo = lo;
+    n_hi = hi & ((1u << t) - 1u);
+  } else {  // 1 .. 31
+    c_lo = (lo >> sh) | (hi << (32u - sh));
+    c_hi = hi >> sh;
+    n_lo = lo & ((1u << sh) - 1u);
+    n_hi = 0u;
+  }
+  conn = c_lo;
+  number = (unsigned long long)n_lo | ((unsigned long long)n_hi << 32);
+  return c_hi == 0u && c_lo < a.n_conns;
+}
+
+// a 64-bit maximum into *w that skips the atomic where it cannot win (a stale
+// load can only be too small, and then the atomic decides)
+__device__ __forceinline__ void retire_max(unsigned long long* w, unsigned long long v) {
+  if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) atomicMax(w, v);
+}
+
+// One lane's key offered to round a.round; keyed: the lane holds a key that
+// counts (an open slot's or a packet's, not QFEC_NO_KEY).
+__device__ __forceinline__ void retire_offer(const RetireArgs& a, unsigned long long key,
+                                             bool keyed, uint32_t lane) {
+  uint32_t conn;
+  unsigned long long num;
+  bool live = retire_split(a, key, conn, num) && keyed;
+  if (live) live = num >= a.conn_mark[conn];
+  if (live && a.round != 0u)  // (0 = nothing left below: num + 1 >= 1)
+    live = num + 1u < a.top[(uint64_t)(a.round - 1u) * a.n_conns + conn];
+  // (all three shuffled before anything is compared: lane_runs' rule; a live
+  // lane under a lane that is not live heads a run whatever the keys are)
+  const uint32_t k_lo = (uint32_t)key, k_hi = (uint32_t)(key >> 32);
+  const uint32_t below_lo = __shfl_up(k_lo, 1), below_hi = __shfl_up(k_hi, 1);
+  const uint32_t below_live = __shfl_up((uint32_t)live, 1);
+  const LaneRun run =
+      lane_runs(live, below_live != 0u && below_lo == k_lo && below_hi == k_hi, lane);
+  if (run.head) retire_max(&a.top[(uint64_t)a.round * a.n_conns + conn], num + 1u);
+}
+
+__global__ __launch_bounds__(kReviveTile) void retire_raise_kernel(RetireArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t n_bad = 0;  // the wave's raises out of range (uniform)
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * kReviveTile; i0 < a.n_raise; i0 += step) {
+    const uint64_t i = i0 + tid;
+    const bool in = i < a.n_raise;
+    const uint64_t ic = in ? i : a.n_raise - 1u;  // (clamped, not masked)
+    const uint32_t conn = a.raise_conn[ic];
+    const unsigned long long mark = a.raise_mark[ic];
+    if (in && conn < a.n_conns) retire_max(&a.conn_mark[conn], mark);
+    n_bad += (uint32_t)__popcll(__ballot(in && conn >= a.n_conns));
+  }
+  const uint32_t t = block_sum(n_bad, lane, wave, s_w);
+  if (tid == 0u && t != 0u) {
+    atomicAdd(&a.tally[4], (unsigned long long)t);
+    atomicOr(a.err, kErrMissingIndex);
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void retire_round_kernel(RetireArgs a) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t s0 = (uint64_t)blockIdx.x * kReviveTile; s0 < a.n_slots; s0 += step) {
+    const uint64_t s = s0 + tid;
+    const bool in = s < a.n_slots;
+    const uint64_t sc = in ? s : a.n_slots - 1u;  // (clamped, not masked)
+    const unsigned long long key = a.slot_key[sc];
+    retire_offer(a, key, in && a.acc_len[sc] != 0 && key != kAssignNoKey, lane);
+  }
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const unsigned long long key = a.pkt_key[in ? p : a.n_packets - 1u];  // (clamped)
+    retire_offer(a, key, in && key != kAssignNoKey, lane);
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void retire_mark_kernel(RetireArgs a) {
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t c = (uint64_t)blockIdx.x * kReviveTile + threadIdx.x; c < a.n_conns; c += step) {
+    // more than max_groups live numbers: the max_groups-th largest is the mark
+    // (it is live, so at or above the old one)
+    const unsigned long long kept = a.top[(uint64_t)(a.max_groups - 1u) * a.n_conns + c];
+    if (a.top[(uint64_t)a.max_groups * a.n_conns + c] != 0ull && kept != 0ull)
+      a.conn_mark[c] = kept - 1u;
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void retire_filter_kernel(RetireArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves * 4];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  // the wave's packets (uniform): refused, keyless, passed, connection out of range
+  uint32_t n[4] = {0, 0, 0, 0};
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const unsigned long long key = a.pkt_key[in ? p : a.n_packets - 1u];  // (clamped, not masked)
+    const bool keyed = in && key != kAssignNoKey;
+    uint32_t conn;
+    unsigned long long num;
+    const bool known = retire_split(a, key, conn, num) && keyed;
+    const bool refused = known && num < a.conn_mark[conn];
+    const bool passed = known && !refused;
+    if (in) a.pkt_key_out[p] = passed ? key : kAssignNoKey;
+    n[0] += (uint32_t)__popcll(__ballot(refused));
+    n[1] += (uint32_t)__popcll(__ballot(in && !keyed));
+    n[2] += (uint32_t)__popcll(__ballot(passed));
+    n[3] += (uint32_t)__popcll(__ballot(keyed && !known));
+  }
+  const uint32_t t = block_sum(n, lane, wave, s_w);
+  if (tid < 4u && t != 0u) {
+    atomicAdd(&a.tally[1u + tid], (unsigned long long)t);
+    if (tid == 3u) atomicOr(a.err, kErrMissingIndex);
+  }
+}
+
+// what the close does with slot s: 1 it closes it (open, keyed, below its
+// connection's mark), 2 its connection is out of range, 0 anything else
+__device__ __forceinline__ uint32_t retire_slot_class(const RetireArgs& a, uint64_t s) {
+  const bool in = s < a.n_slots;
+  const uint64_t sc = in ? s : a.n_slots - 1u;  // (clamped, not masked)
+  const unsigned long long key = a.slot_key[sc];
+  const bool keyed = in && a.acc_len[sc] != 0 && key != kAssignNoKey;
+  uint32_t conn;
+  unsigned long long num;
+  const bool known = retire_split(a, key, conn, num);
+  if (!keyed) return 0u;
+  if (!known) return 2u;
+  return num < a.conn_mark[conn] ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kReviveTile) void retire_classify_kernel(RetireArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t n_bad = 0;  // the wave's open slots with a connection out of range (uniform)
+  const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const uint32_t cls = retire_slot_class(a, tile * kReviveTile + tid);
+    n_bad += (uint32_t)__popcll(__ballot(cls == 2u));
+    const uint32_t t = block_sum((uint32_t)__popcll(__ballot(cls == 1u)), lane, wave, s_w);
+    if (tid == 0u) a.tile_off[tile] = t;
+  }
+  const uint32_t t = block_sum(n_bad, lane, wave, s_w);
+  if (tid == 0u && t != 0u) {
+    atomicAdd(&a.tally[4], (unsigned long long)t);
+    atomicOr(a.err, kErrMissingIndex);
+  }
+}
+
+// One workgroup: tile_off[i] = slots closed in the tiles before i (in place
+// over the tile counts), then counts.  The sum fits 32 bits: n_slots < 2^32.
+__global__ __launch_bounds__(kRvScanBlock) void retire_scan_kernel(RetireArgs a) {
+  __shared__ uint32_t s_w[kRvScanBlock / 64];
+  const uint32_t closed = tile_scan_in_place(
+      a.tile_off, ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile, s_w);
+  if (threadIdx.x == 0u && a.counts) {
+    a.counts[0] = closed;
+    for (uint32_t i = 1; i < 5u; ++i) a.counts[i] = a.tally[i];
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void retire_close_kernel(RetireArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint64_t ntile = ((uint64_t)a.n_slots + kReviveTile - 1) / kReviveTile;
+  for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const uint64_t s = tile * kReviveTile + tid;
+    // (a lane reads and writes the length of its own slot only)
+    const bool closing = retire_slot_class(a, s) == 1u;
+    // the closed slots of the tiles and of the tile's lanes below this one
+    const uint64_t r =
+        (uint64_t)a.tile_off[tile] + block_ballot_rank(__ballot(closing), lane, wave, s_w);
+    if (closing) {
+      a.acc_len[s] = 0;
+      if (a.closed_list && r < a.n_slots) a.closed_list[r] = (uint32_t)s;
+    }
+  }
+}
+
 // The recover body over the work list, L >= 16: lanes, windows and loads as
 // fixed_xor_kernel; workgroup step i takes entries [i * gpb, (i + 1) * gpb).
 // `work` and `totals` are separate restrict parameters so that their loads
@@ -4248,6 +4464,27 @@ hipError_t launch_assign_slots(const AssignArgs& a, hipStream_t s) {
   e = launch_pass(e, assign_free_kernel, stiles, kReviveTile, s, a);
   e = launch_pass(e, assign_open_kernel, ptiles, kReviveTile, s, a);
   e = launch_pass(e, assign_emit_kernel, pgrid, kReviveTile, s, a);
+  return e;
+}
+
+hipError_t launch_retire_groups(const RetireArgs& a0, hipStream_t s) {
+  if (a0.n_packets == 0 && a0.n_slots == 0 && a0.n_raise == 0) return hipSuccess;
+  RetireArgs a = a0;
+  hipError_t e = hipMemsetAsync(a.tally, 0, retire_scratch_zeroed(a.n_conns, a.max_groups), s);
+  const uint32_t pgrid = per_packet_grid(a.n_packets, a.ncu), stiles = tile_grid(a.n_slots);
+  if (a.n_raise != 0)
+    e = launch_pass(e, retire_raise_kernel, per_packet_grid(a.n_raise, a.ncu), kReviveTile, s, a);
+  if (a.max_groups != 0 && a.n_conns != 0 && (a.n_packets != 0 || a.n_slots != 0)) {
+    const uint32_t rgrid = per_packet_grid(std::max<uint64_t>(a.n_packets, a.n_slots), a.ncu);
+    for (a.round = 0; a.round <= a.max_groups; ++a.round)
+      e = launch_pass(e, retire_round_kernel, rgrid, kReviveTile, s, a);
+    a.round = 0;
+    e = launch_pass(e, retire_mark_kernel, per_packet_grid(a.n_conns, a.ncu), kReviveTile, s, a);
+  }
+  if (a.n_packets != 0) e = launch_pass(e, retire_filter_kernel, pgrid, kReviveTile, s, a);
+  if (a.n_slots != 0) e = launch_pass(e, retire_classify_kernel, stiles, kReviveTile, s, a);
+  e = launch_pass(e, retire_scan_kernel, 1, kRvScanBlock, s, a);  // (counts, whatever is empty)
+  if (a.n_slots != 0) e = launch_pass(e, retire_close_kernel, stiles, kReviveTile, s, a);
   return e;
 }
 

@@ -106,6 +106,9 @@ SIGNATURES = [
       C.c_uint32]),
     ("qfec_assign_slots", C.c_int,
      [_vp, _vp, _u8p, C.c_uint64, _vp, _u8p, _vp, C.c_uint64, _vp, _vp, C.c_uint32]),
+    ("qfec_retire_groups", C.c_int,
+     [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp,
+      _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint32]),
     ("qfec_xor_into", C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint32]),
     ("qfec_wire_write_private_header", C.c_size_t, [_vp, _u8p, C.c_size_t]),
     ("qfec_wire_parse_private_header", C.c_size_t,
@@ -609,6 +612,32 @@ class Context:
         rc = self.lib.qfec_assign_slots(self.ctx, _ptr(pkt_key), _ptr(pkt_k), n_packets,
                                         _ptr(slot_key), _ptr(slot_k), _ptr(acc_len), n_slots,
                                         _ptr(pkt_slot_out), _ptr(counts), flags)
+        return self._check(rc)
+
+    def retire_groups(self, pkt_key, n_packets, slot_key, acc_len, n_slots, conn_mark, n_conns,
+                      key_shift, max_groups, pkt_key_out, *, raise_conn=None, raise_mark=None,
+                      n_raise=0, closed_list=None, counts=None, flags=0):
+        """qfec_retire_groups, in front of assign_slots: the one call that
+        reads a key (conn = key >> key_shift, number = the bits below).
+        conn_mark (uint64[n_conns]) holds every connection's watermark and is
+        updated: raised by the turn's thresholds (raise_conn uint32, raise_mark
+        uint64, n_raise of them), then, with max_groups in 1..16, to the
+        max_groups-th largest distinct number at or above it among the
+        connection's open keyed slots (acc_len > 0, slot_key uint64) and keyed
+        packets (pkt_key uint64) where there are more than max_groups.  Every
+        open keyed slot below its mark gets acc_len (uint16[n_slots]) = 0 and
+        is listed ascending in closed_list (uint32[n_slots], optional);
+        pkt_key_out (uint64[n_packets], may be pkt_key) is pkt_key with
+        QFEC_NO_KEY where the number is below the mark, what assign_slots then
+        reads.  counts (uint64[5], optional): slots closed, packets refused,
+        QFEC_NO_KEY, packets passed, connections out of range (the last
+        latched).  Device pointers only; queued on the context's stream
+        (sync() before reading the results)."""
+        rc = self.lib.qfec_retire_groups(self.ctx, _ptr(pkt_key), n_packets, _ptr(slot_key),
+                                         _ptr(acc_len), n_slots, _ptr(conn_mark), n_conns,
+                                         key_shift, max_groups, _ptr(raise_conn),
+                                         _ptr(raise_mark), n_raise, _ptr(pkt_key_out),
+                                         _ptr(closed_list), _ptr(counts), flags)
         return self._check(rc)
 
     def xor_into(self, src, n, dst, *, host=False, mapped=False):
