@@ -42,6 +42,12 @@
  *       STOP_WAITING's threshold drops every group waiting for a packet below
  *       it, for good) and GetFecGroup's kMaxFecGroups eviction, for a whole
  *       turn in front of the assign: per-connection watermarks.
+ *   qfec_parse_opened / qfec_write_private_headers
+ *       are QuicFramer::ProcessAuthenticatedHeader (quic_framer.cc:1102-1141,
+ *       run over the DECRYPTED buffer: the private flags and the FEC group
+ *       offset byte are encrypted) and its writer, for a whole turn: the
+ *       opened packets' first bytes become the keys, positions and body
+ *       tables the calls above read.
  *   qfec_recover_batch / _strided / qfec_recover_ragged
  *       replaces QuicFecGroup::UpdateFec + Update(received) + CanRevive() +
  *       Revive().  Receive-side hook: QuicConnection::ProcessValidatedPacket
@@ -529,8 +535,10 @@ int qfec_revive_accumulated(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stri
  * a packet number already in received_packets_; folded twice it cancels out of
  * the row).  A receiver's turn is open -> qfec_admit_ragged ->
  * qfec_accumulate_ragged -> qfec_revive_tracked on one stream, with no sync
- * and no host decision in between.  The position is the cleartext FEC group
- * offset byte; the slot is the host's lookup, or qfec_assign_slots' (below),
+ * and no host decision in between.  The position is the FEC group offset byte,
+ * which lies in the encrypted part of the packet: qfec_parse_opened (below)
+ * reads it on the device; the slot is the host's lookup, or qfec_assign_slots'
+ * (below),
  * which also lists what then remains with the host.
  *
  * qfec_admit_ragged never reads a payload byte.  pkt_off, pkt_len and grp_ptr
@@ -634,7 +642,9 @@ int qfec_revive_tracked(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride, 
  * qfec_bin_arrivals -> qfec_admit_ragged -> qfec_accumulate_ragged ->
  * qfec_revive_tracked on one stream, with no sync and no host decision in
  * between.  The slots come from the host or from qfec_assign_slots (below);
- * the position is the cleartext FEC group offset byte.
+ * the position is the FEC group offset byte, encrypted on the wire and read
+ * from the opened packet by qfec_parse_opened (below), whose body_off_out,
+ * body_len_out and pkt_idx_out this call takes as pkt_off, pkt_len and pkt_idx.
  *
  * Inputs, n_packets records in arrival order: pkt_slot[p] the slot of the
  * packet's group, or QFEC_NO_SLOT for a packet that is no candidate
@@ -689,10 +699,11 @@ int qfec_bin_arrivals(qfec_ctx* ctx, const uint32_t* pkt_slot, const uint64_t* p
 
 /* Slots found or opened on the device: the group_map_ lookup and insert of
  * QuicConnection::GetFecGroup (quic_connection.cc:1388-1392), for a whole turn
- * at once.  The host appends one 64-bit group key per packet, built from what
- * the cleartext header gives it (suggested: connection index << 40 | group
- * number, the group number being the packet number minus the FEC group offset
- * byte); this call resolves every key to the slot of its open group, or opens
+ * at once.  Every packet has one 64-bit group key (suggested: connection index
+ * << 40 | group number, the group number being the cleartext packet number
+ * minus the FEC group offset byte; that byte is encrypted, so the key is
+ * qfec_parse_opened's to build, below, or the host's where the protection is
+ * NULL); this call resolves every key to the slot of its open group, or opens
  * a group in a free slot, and writes the pkt_slot array qfec_bin_arrivals
  * reads.  The turn is open -> qfec_assign_slots -> qfec_bin_arrivals ->
  * qfec_admit_ragged -> qfec_accumulate_ragged -> qfec_revive_tracked on one
@@ -737,9 +748,9 @@ int qfec_bin_arrivals(qfec_ctx* ctx, const uint32_t* pkt_slot, const uint64_t* p
  * acc_len before the next assign: until then the slot still counts as free.
  * If every candidate of a new group fails its tag nothing was folded, and the
  * slot is free again with nothing lost.
- * What stays with the host: the key and the position (pkt_idx) from the
- * cleartext header, and which packets are candidates at all, expressed through
- * QFEC_NO_KEY.  A late duplicate of a released group would open it anew under
+ * What stays with the host: which packets are candidates at all, expressed
+ * through QFEC_NO_KEY (the key and the position, pkt_idx, come from the
+ * encrypted private header: qfec_parse_opened, below).  A late duplicate of a released group would open it anew under
  * its key: the per-connection watermark below which a group is never reopened,
  * the forced closes and the bound on a connection's open groups are
  * qfec_retire_groups' (below), which runs in front of this call and hands it
@@ -818,8 +829,10 @@ int qfec_assign_slots(qfec_ctx* ctx, const uint64_t* pkt_key, const uint8_t* pkt
  * Ordering: the retire runs before the assign of the same turn on the same
  * stream.  The assign sees the slots closed here as free and reuses them with
  * nothing cleared; between the two the host does nothing.
- * What stays with the host: the key and the position from the cleartext
- * header; which packets are candidates at all; and raising a mark past a group
+ * What stays with the host: the packet number and the connection from the
+ * cleartext public header (the key and the position come from the encrypted
+ * private header, through qfec_parse_opened, below); which packets are
+ * candidates at all; and raising a mark past a group
  * that finished or was revived ahead of older open ones, for which it has
  * revived_list and status and feeds the raise list.
  * Where the turn differs from the per-packet reference: packets of a group
@@ -849,6 +862,118 @@ int qfec_retire_groups(qfec_ctx* ctx, const uint64_t* pkt_key, uint64_t n_packet
                        uint32_t max_groups, const uint32_t* raise_conn,
                        const uint64_t* raise_mark, uint64_t n_raise, uint64_t* pkt_key_out,
                        uint32_t* closed_list, uint64_t* counts, uint32_t flags);
+
+/* Private headers on the device: QuicFramer::ProcessAuthenticatedHeader
+ * (quic_framer.cc:1102-1141) for a whole turn.  The framer decrypts first
+ * (ProcessDataPacket, quic_framer.cc:605-629) and parses the private flags and
+ * the FEC group offset from the DECRYPTED buffer: GetStartOfEncryptedData puts
+ * both inside the encrypted region.  For a packet opened on the device
+ * (qfec_chacha20poly1305_open_batch, qfec_aes128gcm_open_batch) whether it is
+ * in a group, which group (packet number - offset), its position (the offset)
+ * and whether it is the FEC packet therefore lie in device memory.  This call
+ * reads them there, and the turn is open -> qfec_parse_opened ->
+ * qfec_retire_groups -> qfec_assign_slots -> qfec_bin_arrivals ->
+ * qfec_admit_ragged -> qfec_accumulate_ragged -> qfec_revive_tracked on one
+ * stream, with no sync and no host decision in between; the bin reads
+ * body_off_out, body_len_out, pkt_idx_out and pkt_ok.
+ *
+ * Inputs, n_packets records in arrival order: packet p's plaintext is
+ * pkt_len[p] bytes at bytes + pkt_off[p] (the open call's out and out_off, with
+ * in_len - 12), packet_number[p] its full packet number (what the open call
+ * was given), pkt_conn[p] its connection index, pkt_ok[p] the open call's
+ * verdict (pkt_ok NULL: all verified).
+ * The rule, per packet, checked in this order; hdr_out[p] is the class:
+ *   pkt_ok given and pkt_ok[p] == 0        QFEC_HDR_FAILED.  No payload byte of
+ *                                          the packet is read (the open left
+ *                                          stale bytes there).
+ *   pkt_len[p] == 0                        QFEC_HDR_NO_FLAGS ("Unable to read
+ *                                          private flags.")
+ *   flags byte above the version's maximum QFEC_HDR_ILLEGAL_FLAGS (7 for
+ *                                          quic_version <= 31, 1 above)
+ *   FEC_GROUP bit (2) set and, in turn:
+ *     pkt_len[p] < 2                       QFEC_HDR_NO_OFFSET
+ *     offset >= packet_number[p]           QFEC_HDR_BAD_OFFSET
+ *     pkt_len[p] == 2                      QFEC_HDR_EMPTY: the framer's "Packet
+ *                                          has no frames."; the admit would
+ *                                          otherwise latch on a length of 0
+ *     pkt_conn[p] >> (64 - key_shift) != 0, (packet_number[p] - offset) >>
+ *     key_shift != 0, or the key built
+ *     equals QFEC_NO_KEY                   QFEC_HDR_RANGE: a caller error,
+ *                                          latched on the device and returned
+ *                                          by the next qfec_sync as
+ *                                          -QUIC_INVALID_FEC_DATA, as
+ *                                          qfec_retire_groups latches a
+ *                                          connection out of range
+ *   otherwise                              the flags byte itself, 0..7: accepted
+ * The outputs follow from the class, a pure function of the inputs:
+ *   accepted, in a group: pkt_key_out[p] = pkt_conn[p] << key_shift |
+ *     (packet_number[p] - offset); pkt_idx_out[p] = offset, the position (0 ..
+ *     K - 1 a data packet, K the FEC packet); body_off_out[p] = pkt_off[p] + 2,
+ *     body_len_out[p] = pkt_len[p] - 2: what QuicFecGroup::Update folds, and an
+ *     FEC packet's redundancy.
+ *   accepted, in no group (flags 4 and 5, FEC without a group, included: the
+ *     reference framer accepts them): pkt_key_out[p] = QFEC_NO_KEY,
+ *     pkt_idx_out[p] = 0, body_off_out[p] = pkt_off[p] + 1, body_len_out[p] =
+ *     pkt_len[p] - 1.
+ *   every other class: pkt_key_out[p] = QFEC_NO_KEY, pkt_idx_out[p] = 0,
+ *     body_off_out[p] = pkt_off[p], body_len_out[p] = 0.
+ *   entropy_out[p] (may be NULL) = (flags & 1) << (packet_number[p] % 8) when
+ *     accepted, else 0: GetPacketEntropyHash, as qfec_entropy_cumulative_batch
+ *     reads it.
+ * counts[0..5] (may be NULL), written, not added to: data packets in a group;
+ * FEC packets in a group; accepted outside any group; FAILED; headers rejected
+ * (NO_FLAGS, ILLEGAL_FLAGS, NO_OFFSET, BAD_OFFSET, EMPTY); RANGE.  Every packet
+ * is counted in exactly one.
+ * No byte outside [pkt_off[p], pkt_off[p] + pkt_len[p]) is read, whatever the
+ * alignment of pkt_off[p].
+ * Where this differs from the reference: a rejected header is a per-packet
+ * result here (the framer raises QUIC_INVALID_PACKET_HEADER and the connection
+ * closes; that policy stays with the host, which has hdr_out and counts[4]);
+ * EMPTY is the framer's verdict one step later, taken here because a body of 0
+ * bytes must not reach the admit.
+ * What stays with the host: the packet number and the connection, which come
+ * from the genuinely cleartext public header; K, the negotiated group size, in
+ * pkt_k; and policy.
+ * Refused on the host (nothing launched, nothing written): QFEC_PTR_HOST,
+ * QFEC_PTR_MAPPED or QFEC_ASYNC; a NULL buffer other than pkt_ok, entropy_out
+ * and counts; key_shift outside 1..63; quic_version outside 1..33; n_packets
+ * >= 2^32 (QFEC_ERR_INTERNAL, in that order).  n_packets == 0 succeeds before
+ * the buffers are looked at (counts, if given, receives six zeroes).
+ * QFEC_CACHED and QFEC_SMALL_GROUPS are accepted and change nothing.  Device
+ * pointers only; the call only queues work on the context's stream (a memset
+ * of counts and one kernel), never waits, never reads anything back and needs
+ * no scratch. */
+#define QFEC_HDR_FAILED 0x80u        /* hdr_out: pkt_ok[p] == 0, nothing read */
+#define QFEC_HDR_NO_FLAGS 0x81u      /* no private flags byte */
+#define QFEC_HDR_ILLEGAL_FLAGS 0x82u /* flags above the version's maximum */
+#define QFEC_HDR_NO_OFFSET 0x83u     /* FEC_GROUP set, no offset byte */
+#define QFEC_HDR_BAD_OFFSET 0x84u    /* offset >= packet number */
+#define QFEC_HDR_RANGE 0x85u         /* connection or group number does not fit the key */
+#define QFEC_HDR_EMPTY 0x86u         /* in a group, nothing behind the header */
+int qfec_parse_opened(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt_off,
+                      const uint16_t* pkt_len, const uint64_t* packet_number,
+                      const uint32_t* pkt_conn, const uint8_t* pkt_ok, uint64_t n_packets,
+                      int quic_version, uint32_t key_shift, uint64_t* pkt_key_out,
+                      uint8_t* pkt_idx_out, uint64_t* body_off_out, uint16_t* body_len_out,
+                      uint8_t* hdr_out, uint8_t* entropy_out, uint64_t* counts, uint32_t flags);
+
+/* The sender's mirror: WriteFecPrivateHeader over a batch, in front of the
+ * seal.  hdr[p] (the private flags byte: 1 entropy, 2 FEC_GROUP, 4 FEC) is
+ * written at bytes + pkt_off[p] and, where the FEC_GROUP bit (2) is set,
+ * fec_offset[p] behind it; body_off_out[p] (may be NULL) = pkt_off[p] + 1 or +
+ * 2: where the frames go, or where qfec_emit_accumulated is to put the
+ * redundancy.  A record that WriteFecPrivateHeader refuses -- FEC without a
+ * group, or flags above the version's maximum (7 for quic_version <= 31, 1
+ * above) -- writes no byte, gets body_off_out[p] = pkt_off[p], and is latched
+ * (the next qfec_sync returns -QUIC_INVALID_FEC_DATA).  counts[0..1] (may be
+ * NULL), written, not added to: records written, records refused.  Two
+ * records must not overlap.  Refusals on the host, n_packets == 0, the flags
+ * and the queueing as qfec_parse_opened; only body_off_out and counts may be
+ * NULL. */
+int qfec_write_private_headers(qfec_ctx* ctx, uint8_t* bytes, const uint64_t* pkt_off,
+                               const uint8_t* hdr, const uint8_t* fec_offset,
+                               uint64_t n_packets, int quic_version, uint64_t* body_off_out,
+                               uint64_t* counts, uint32_t flags);
 
 /* ---- single buffer ------------------------------------------------------ */
 /* out[j] ^= in[j] for j < n (QuicFecGroupInterface::XorBuffers). */

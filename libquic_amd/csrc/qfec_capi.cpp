@@ -2505,6 +2505,101 @@ int qfec_retire_groups(qfec_ctx* ctx, const uint64_t* pkt_key, uint64_t n_packet
   return revive_scratch_release(ctx);
 }
 
+namespace {
+
+// the highest legal private flags byte (quic_protocol.h:343-358): above
+// version 31 only the entropy bit
+uint32_t max_private_flags(int quic_version) { return quic_version > 31 ? 1u : 7u; }
+
+int check_quic_version(qfec_ctx* ctx, const char* what, int quic_version) {
+  if (quic_version >= 1 && quic_version <= 33) return QFEC_OK;
+  return fail(ctx, QFEC_ERR_INTERNAL,
+              "%s: quic_version %d outside [1, 33] (no private flags byte above 33)", what,
+              quic_version);
+}
+
+}  // namespace
+
+// QuicFramer::ProcessAuthenticatedHeader (quic_framer.cc:1102-1141) over the
+// opened packets of a turn: the private flags and the FEC group offset, both
+// encrypted on the wire, become the keys, positions and body tables the retire,
+// the assign and the bin read.  One memset and one kernel on the stream, no
+// scratch; every check that needs the tables is the kernel's.
+int qfec_parse_opened(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* pkt_off,
+                      const uint16_t* pkt_len, const uint64_t* packet_number,
+                      const uint32_t* pkt_conn, const uint8_t* pkt_ok, uint64_t n_packets,
+                      int quic_version, uint32_t key_shift, uint64_t* pkt_key_out,
+                      uint8_t* pkt_idx_out, uint64_t* body_off_out, uint16_t* body_len_out,
+                      uint8_t* hdr_out, uint8_t* entropy_out, uint64_t* counts, uint32_t flags) {
+  const char* const what = "parse opened";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_device_only(ctx, what, flags))) return rc;
+  if (n_packets == 0) return zero_counts(ctx, counts, 6);
+  if (!bytes || !pkt_off || !pkt_len || !packet_number || !pkt_conn || !pkt_key_out ||
+      !pkt_idx_out || !body_off_out || !body_len_out || !hdr_out)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: null buffer (only pkt_ok, entropy_out and counts may be NULL)", what);
+  if (key_shift < 1 || key_shift > 63)
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: key_shift %u outside [1, 63]", what, key_shift);
+  if ((rc = check_quic_version(ctx, what, quic_version))) return rc;
+  if (n_packets >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: 2^32 or more packets (packet indices are 32 bits)", what);
+  qfec::ParseArgs a{};
+  a.bytes = bytes;
+  a.pkt_off = pkt_off;
+  a.pkt_len = pkt_len;
+  a.packet_number = reinterpret_cast<const unsigned long long*>(packet_number);
+  a.pkt_conn = pkt_conn;
+  a.pkt_ok = pkt_ok;
+  a.n_packets = n_packets;
+  a.max_flags = max_private_flags(quic_version);
+  a.key_shift = key_shift;
+  a.pkt_key_out = reinterpret_cast<unsigned long long*>(pkt_key_out);
+  a.pkt_idx_out = pkt_idx_out;
+  a.body_off_out = body_off_out;
+  a.body_len_out = body_len_out;
+  a.hdr_out = hdr_out;
+  a.entropy_out = entropy_out;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.err = ctx->d_err;
+  a.ncu = ctx->ncu;
+  QFEC_HIP(ctx, qfec::launch_parse_opened(a, ctx->stream));
+  return QFEC_OK;
+}
+
+// WriteFecPrivateHeader over a batch, in front of the seal: the flags byte and,
+// in a group, the offset byte at every record's place in the arena.
+int qfec_write_private_headers(qfec_ctx* ctx, uint8_t* bytes, const uint64_t* pkt_off,
+                               const uint8_t* hdr, const uint8_t* fec_offset,
+                               uint64_t n_packets, int quic_version, uint64_t* body_off_out,
+                               uint64_t* counts, uint32_t flags) {
+  const char* const what = "write private headers";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_device_only(ctx, what, flags))) return rc;
+  if (n_packets == 0) return zero_counts(ctx, counts, 2);
+  if (!bytes || !pkt_off || !hdr || !fec_offset)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: null buffer (only body_off_out and counts may be NULL)", what);
+  if ((rc = check_quic_version(ctx, what, quic_version))) return rc;
+  if (n_packets >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: 2^32 or more packets (packet indices are 32 bits)", what);
+  qfec::WriteHeadersArgs a{};
+  a.bytes = bytes;
+  a.pkt_off = pkt_off;
+  a.hdr = hdr;
+  a.fec_offset = fec_offset;
+  a.n_packets = n_packets;
+  a.max_flags = max_private_flags(quic_version);
+  a.body_off_out = body_off_out;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.err = ctx->d_err;
+  a.ncu = ctx->ncu;
+  QFEC_HIP(ctx, qfec::launch_write_private_headers(a, ctx->stream));
+  return QFEC_OK;
+}
+
 // qfec_revive_accumulated with the group's K and map kept per slot, where
 // qfec_admit_ragged maintains them.
 int qfec_revive_tracked(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride, uint16_t* acc_len,

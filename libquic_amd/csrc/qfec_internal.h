@@ -463,6 +463,50 @@ inline void retire_scratch_layout(RetireArgs& a, void* block) {
 // of n_packets, n_slots and n_raise are 0.
 hipError_t launch_retire_groups(const RetireArgs& a, hipStream_t s);
 
+// qfec_parse_opened: QuicFramer::ProcessAuthenticatedHeader over the opened
+// packets of a turn, in front of the retire (rule as include/qfec.h).  No
+// scratch: the six tallies are added into counts, zeroed in front of the pass.
+constexpr uint32_t kHdrFailed = 0x80, kHdrNoFlags = 0x81, kHdrIllegalFlags = 0x82,
+                   kHdrNoOffset = 0x83, kHdrBadOffset = 0x84, kHdrRange = 0x85, kHdrEmpty = 0x86;
+constexpr uint32_t kPrivateFlagEntropy = 1, kPrivateFlagFecGroup = 2, kPrivateFlagFec = 4;
+struct ParseArgs {
+  const uint8_t* bytes;
+  const uint64_t* pkt_off;
+  const uint16_t* pkt_len;
+  const unsigned long long* packet_number;
+  const uint32_t* pkt_conn;
+  const uint8_t* pkt_ok;  // nullable: all verified
+  uint64_t n_packets;     // 0 < n_packets < 2^32
+  uint32_t max_flags;     // the version's highest legal flags byte: 7 or 1
+  uint32_t key_shift;     // 1..63
+  unsigned long long* pkt_key_out;
+  uint8_t* pkt_idx_out;
+  uint64_t* body_off_out;
+  uint16_t* body_len_out;
+  uint8_t* hdr_out;
+  uint8_t* entropy_out;        // nullable
+  unsigned long long* counts;  // nullable: [data, FEC, no group, failed, rejected, range]
+  uint32_t* err;
+  uint32_t ncu;
+};
+// One memset (with counts) and one launch on s.  n_packets > 0.
+hipError_t launch_parse_opened(const ParseArgs& a, hipStream_t s);
+
+// qfec_write_private_headers: WriteFecPrivateHeader over a batch.
+struct WriteHeadersArgs {
+  uint8_t* bytes;
+  const uint64_t* pkt_off;
+  const uint8_t* hdr;
+  const uint8_t* fec_offset;
+  uint64_t n_packets;  // 0 < n_packets < 2^32
+  uint32_t max_flags;
+  uint64_t* body_off_out;      // nullable
+  unsigned long long* counts;  // nullable: [written, refused]
+  uint32_t* err;
+  uint32_t ncu;
+};
+hipError_t launch_write_private_headers(const WriteHeadersArgs& a, hipStream_t s);
+
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch
 // per batch (the launch is most of a small flush's connection-thread cost).

@@ -2036,6 +2036,122 @@ __global__ __launch_bounds__(kReviveTile) void retire_close_kernel(RetireArgs a)
   }
 }
 
+// ---------------------------------------------------------------------------
+// Private headers on the device (qfec_parse_opened,
+// qfec_write_private_headers): QuicFramer::ProcessAuthenticatedHeader and
+// WriteFecPrivateHeader over a turn's opened packets, in front of the retire.
+// ---------------------------------------------------------------------------
+// One pass, one lane per packet: the record (clamped for the lanes past the
+// end, which then classify the last packet once more and store nothing), at
+// most two bytes of the packet, the class, six stores.  A byte is loaded only
+// under the predicate that puts it inside [pkt_off, pkt_off + pkt_len) of a
+// packet that verified; the two are byte loads, so no alignment matters.  The
+// key is built, and its range checked, in 32-bit halves as retire_split takes
+// it apart (the gfx950 64-bit shift hazard).  Tallies by ballot, block_sum and
+// one atomic per workgroup and class into counts, zeroed in front of the pass.
+__global__ __launch_bounds__(kReviveTile) void parse_opened_kernel(ParseArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves * 6];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  // the wave's packets (uniform): data, FEC, outside a group, failed, rejected, range
+  uint32_t n[6] = {0, 0, 0, 0, 0, 0};
+  const uint32_t sh = a.key_shift;
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const uint64_t pc = in ? p : a.n_packets - 1u;  // (clamped, not masked)
+    const uint64_t off = a.pkt_off[pc];
+    const uint32_t len = a.pkt_len[pc];
+    const unsigned long long pn = a.packet_number[pc];
+    const uint32_t conn = a.pkt_conn[pc];
+    const bool ok = a.pkt_ok == nullptr || a.pkt_ok[pc] != 0;
+    uint32_t b0 = 0u, b1 = 0u;
+    if (ok && len >= 1u) b0 = a.bytes[off];
+    if (ok && len >= 2u) b1 = a.bytes[off + 1u];
+    const bool grouped = (b0 & kPrivateFlagFecGroup) != 0u;
+    // the key, and whether its parts fit: conn below 2^(64 - sh), group below 2^sh
+    const unsigned long long group = pn - b1;  // (read only where b1 < pn)
+    const uint32_t g_lo = (uint32_t)group, g_hi = (uint32_t)(group >> 32);
+    uint32_t k_lo, k_hi;
+    bool fits;
+    if (sh >= 32u) {
+      const uint32_t t = sh - 32u;  // 0 .. 31
+      fits = (t == 0u || (conn >> (32u - t)) == 0u) && (g_hi >> t) == 0u;
+      k_lo = g_lo;
+      k_hi = (conn << t) | g_hi;
+    } else {  // 1 .. 31: any 32-bit connection fits the 64 - sh bits above
+      fits = g_hi == 0u && (g_lo >> sh) == 0u;
+      k_lo = (conn << sh) | g_lo;
+      k_hi = conn >> (32u - sh);
+    }
+    const unsigned long long key = (unsigned long long)k_lo | ((unsigned long long)k_hi << 32);
+    uint32_t cls;
+    if (!ok) cls = kHdrFailed;
+    else if (len == 0u) cls = kHdrNoFlags;
+    else if (b0 > a.max_flags) cls = kHdrIllegalFlags;
+    else if (!grouped) cls = b0;
+    else if (len < 2u) cls = kHdrNoOffset;
+    else if ((unsigned long long)b1 >= pn) cls = kHdrBadOffset;
+    else if (len == 2u) cls = kHdrEmpty;
+    else if (!fits || key == kAssignNoKey) cls = kHdrRange;
+    else cls = b0;
+    const bool accepted = cls < kHdrFailed, keyed = accepted && grouped;
+    const uint32_t used = keyed ? 2u : accepted ? 1u : 0u;
+    if (in) {
+      a.pkt_key_out[p] = keyed ? key : kAssignNoKey;
+      a.pkt_idx_out[p] = (uint8_t)(keyed ? b1 : 0u);
+      a.body_off_out[p] = off + used;
+      a.body_len_out[p] = (uint16_t)(accepted ? len - used : 0u);
+      a.hdr_out[p] = (uint8_t)cls;
+      if (a.entropy_out)
+        a.entropy_out[p] =
+            (uint8_t)(accepted ? (b0 & kPrivateFlagEntropy) << ((uint32_t)pn & 7u) : 0u);
+    }
+    const bool fec = (b0 & kPrivateFlagFec) != 0u;
+    n[0] += (uint32_t)__popcll(__ballot(in && keyed && !fec));
+    n[1] += (uint32_t)__popcll(__ballot(in && keyed && fec));
+    n[2] += (uint32_t)__popcll(__ballot(in && accepted && !keyed));
+    n[3] += (uint32_t)__popcll(__ballot(in && cls == kHdrFailed));
+    n[4] += (uint32_t)__popcll(__ballot(in && !accepted && cls != kHdrFailed && cls != kHdrRange));
+    n[5] += (uint32_t)__popcll(__ballot(in && cls == kHdrRange));
+  }
+  const uint32_t t = block_sum(n, lane, wave, s_w);
+  if (tid < 6u && t != 0u) {
+    if (a.counts) atomicAdd(&a.counts[tid], (unsigned long long)t);
+    if (tid == 5u) atomicOr(a.err, kErrMissingIndex);
+  }
+}
+
+// The sender's mirror, one lane per record: the flags byte and, in a group,
+// the offset byte behind it; a record WriteFecPrivateHeader refuses (FEC
+// without a group, flags above the version's maximum) stores no byte.
+__global__ __launch_bounds__(kReviveTile) void write_headers_kernel(WriteHeadersArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves * 2];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t n[2] = {0, 0};  // the wave's records (uniform): written, refused
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const uint64_t pc = in ? p : a.n_packets - 1u;  // (clamped, not masked)
+    const uint64_t off = a.pkt_off[pc];
+    const uint32_t h = a.hdr[pc], fo = a.fec_offset[pc];
+    const bool grouped = (h & kPrivateFlagFecGroup) != 0u;
+    const bool refused = h > a.max_flags || ((h & kPrivateFlagFec) != 0u && !grouped);
+    const bool writes = in && !refused;
+    if (writes) a.bytes[off] = (uint8_t)h;
+    if (writes && grouped) a.bytes[off + 1u] = (uint8_t)fo;
+    if (in && a.body_off_out) a.body_off_out[p] = off + (refused ? 0u : grouped ? 2u : 1u);
+    n[0] += (uint32_t)__popcll(__ballot(writes));
+    n[1] += (uint32_t)__popcll(__ballot(in && refused));
+  }
+  const uint32_t t = block_sum(n, lane, wave, s_w);
+  if (tid < 2u && t != 0u) {
+    if (a.counts) atomicAdd(&a.counts[tid], (unsigned long long)t);
+    if (tid == 1u) atomicOr(a.err, kErrMissingIndex);
+  }
+}
+
 // The recover body over the work list, L >= 16: lanes, windows and loads as
 // fixed_xor_kernel; workgroup step i takes entries [i * gpb, (i + 1) * gpb).
 // `work` and `totals` are separate restrict parameters so that their loads
@@ -4486,6 +4602,18 @@ hipError_t launch_retire_groups(const RetireArgs& a0, hipStream_t s) {
   e = launch_pass(e, retire_scan_kernel, 1, kRvScanBlock, s, a);  // (counts, whatever is empty)
   if (a.n_slots != 0) e = launch_pass(e, retire_close_kernel, stiles, kReviveTile, s, a);
   return e;
+}
+
+hipError_t launch_parse_opened(const ParseArgs& a, hipStream_t s) {
+  if (a.n_packets == 0) return hipSuccess;
+  hipError_t e = a.counts ? hipMemsetAsync(a.counts, 0, 6 * sizeof(uint64_t), s) : hipSuccess;
+  return launch_pass(e, parse_opened_kernel, per_packet_grid(a.n_packets, a.ncu), kReviveTile, s, a);
+}
+
+hipError_t launch_write_private_headers(const WriteHeadersArgs& a, hipStream_t s) {
+  if (a.n_packets == 0) return hipSuccess;
+  hipError_t e = a.counts ? hipMemsetAsync(a.counts, 0, 2 * sizeof(uint64_t), s) : hipSuccess;
+  return launch_pass(e, write_headers_kernel, per_packet_grid(a.n_packets, a.ncu), kReviveTile, s, a);
 }
 
 hipError_t launch_accumulate_ragged(const AccumulateRaggedArgs& a0, hipStream_t s) {

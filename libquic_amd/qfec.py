@@ -39,6 +39,13 @@ QFEC_PKT_DUPLICATE = 2
 QFEC_PKT_INVALID = 3
 QFEC_NO_SLOT = 0xFFFFFFFF
 QFEC_NO_KEY = 0xFFFFFFFFFFFFFFFF
+QFEC_HDR_FAILED = 0x80
+QFEC_HDR_NO_FLAGS = 0x81
+QFEC_HDR_ILLEGAL_FLAGS = 0x82
+QFEC_HDR_NO_OFFSET = 0x83
+QFEC_HDR_BAD_OFFSET = 0x84
+QFEC_HDR_RANGE = 0x85
+QFEC_HDR_EMPTY = 0x86
 MAX_PACKET_SIZE = 1452
 DEFAULT_MAX_PACKET_SIZE = 1350
 MAX_GROUP_PACKETS = 255
@@ -109,6 +116,11 @@ SIGNATURES = [
     ("qfec_retire_groups", C.c_int,
      [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp,
       _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint32]),
+    ("qfec_parse_opened", C.c_int,
+     [_vp, _u8p, _vp, _vp, _vp, _vp, _u8p, C.c_uint64, C.c_int, C.c_uint32, _vp, _u8p, _vp, _vp,
+      _u8p, _u8p, _vp, C.c_uint32]),
+    ("qfec_write_private_headers", C.c_int,
+     [_vp, _u8p, _vp, _u8p, _u8p, C.c_uint64, C.c_int, _vp, _vp, C.c_uint32]),
     ("qfec_xor_into", C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint32]),
     ("qfec_wire_write_private_header", C.c_size_t, [_vp, _u8p, C.c_size_t]),
     ("qfec_wire_parse_private_header", C.c_size_t,
@@ -638,6 +650,51 @@ class Context:
                                          key_shift, max_groups, _ptr(raise_conn),
                                          _ptr(raise_mark), n_raise, _ptr(pkt_key_out),
                                          _ptr(closed_list), _ptr(counts), flags)
+        return self._check(rc)
+
+    def parse_opened(self, data, pkt_off, pkt_len, packet_number, pkt_conn, n_packets,
+                     quic_version, key_shift, pkt_key_out, pkt_idx_out, body_off_out,
+                     body_len_out, hdr_out, *, pkt_ok=None, entropy_out=None, counts=None,
+                     flags=0):
+        """qfec_parse_opened, in front of retire_groups: the private flags and
+        the FEC group offset byte, encrypted on the wire, read from the opened
+        packets.  Packet p's plaintext is pkt_len[p] (uint16) bytes at data +
+        pkt_off[p] (uint64); packet_number (uint64) and pkt_conn (uint32) come
+        from the public header, pkt_ok (uint8, optional) from the open call.
+        hdr_out (uint8[n_packets]) is the flags byte, 0..7, of an accepted
+        header, or a QFEC_HDR_* class (a FAILED packet's bytes are not read).
+        In a group: pkt_key_out (uint64) = pkt_conn << key_shift |
+        (packet_number - offset), pkt_idx_out (uint8) = offset, body_off_out
+        (uint64) and body_len_out (uint16) the bytes behind the two header
+        bytes; outside one QFEC_NO_KEY, 0 and the bytes behind the flags byte;
+        a refused packet QFEC_NO_KEY, 0, pkt_off and 0.  entropy_out (uint8,
+        optional): the packet's entropy hash, as entropy_cumulative reads it.
+        counts (uint64[6], optional): data packets and FEC packets in a group,
+        accepted outside any group, FAILED, headers rejected, RANGE (a
+        connection or group number that does not fit the key: latched).
+        Device pointers only; queued on the context's stream (sync() before
+        reading the results)."""
+        rc = self.lib.qfec_parse_opened(self.ctx, _ptr(data), _ptr(pkt_off), _ptr(pkt_len),
+                                        _ptr(packet_number), _ptr(pkt_conn), _ptr(pkt_ok),
+                                        n_packets, quic_version, key_shift, _ptr(pkt_key_out),
+                                        _ptr(pkt_idx_out), _ptr(body_off_out),
+                                        _ptr(body_len_out), _ptr(hdr_out), _ptr(entropy_out),
+                                        _ptr(counts), flags)
+        return self._check(rc)
+
+    def write_private_headers(self, data, pkt_off, hdr, fec_offset, n_packets, quic_version, *,
+                              body_off_out=None, counts=None, flags=0):
+        """qfec_write_private_headers, in front of the seal: hdr[p] (uint8, the
+        private flags byte) written at data + pkt_off[p] (uint64) and, where
+        its FEC_GROUP bit is set, fec_offset[p] (uint8) behind it.
+        body_off_out (uint64, optional) is where the frames or the redundancy
+        go: pkt_off + 1 or + 2.  A record with FEC and no group, or with flags
+        above the version's maximum, writes no byte, gets pkt_off and is
+        latched.  counts (uint64[2], optional): written, refused.  Device
+        pointers only; queued on the context's stream."""
+        rc = self.lib.qfec_write_private_headers(self.ctx, _ptr(data), _ptr(pkt_off), _ptr(hdr),
+                                                 _ptr(fec_offset), n_packets, quic_version,
+                                                 _ptr(body_off_out), _ptr(counts), flags)
         return self._check(rc)
 
     def xor_into(self, src, n, dst, *, host=False, mapped=False):
