@@ -48,6 +48,12 @@
  *       offset byte are encrypted) and its writer, for a whole turn: the
  *       opened packets' first bytes become the keys, positions and body
  *       tables the calls above read.
+ *   qfec_record_received / qfec_build_acks
+ *       are QuicReceivedPacketManager with its EntropyTracker
+ *       (RecordPacketReceived, the patch's RecordPacketRevived,
+ *       UpdatePacketInformationSentByPeer; GetUpdatedAckFrame and EntropyHash),
+ *       for a whole turn behind the revive: the parse's verdicts and entropy
+ *       bits and the revive's results become the ack frames' content.
  *   qfec_recover_batch / _strided / qfec_recover_ragged
  *       replaces QuicFecGroup::UpdateFec + Update(received) + CanRevive() +
  *       Revive().  Receive-side hook: QuicConnection::ProcessValidatedPacket
@@ -782,7 +788,8 @@ int qfec_assign_slots(qfec_ctx* ctx, const uint64_t* pkt_key, const uint8_t* pkt
  * a group older than all it keeps.  This call applies both to a whole turn, in
  * front of the assign: the turn is open -> qfec_retire_groups ->
  * qfec_assign_slots -> qfec_bin_arrivals -> qfec_admit_ragged ->
- * qfec_accumulate_ragged -> qfec_revive_tracked on one stream, with no sync and
+ * qfec_accumulate_ragged -> qfec_revive_tracked (-> qfec_record_received ->
+ * qfec_build_acks, below) on one stream, with no sync and
  * no host decision in between.  Per packet the host supplies what the header
  * gives, per connection only the STOP_WAITING thresholds of the turn.
  *
@@ -873,8 +880,9 @@ int qfec_retire_groups(qfec_ctx* ctx, const uint64_t* pkt_key, uint64_t n_packet
  * and whether it is the FEC packet therefore lie in device memory.  This call
  * reads them there, and the turn is open -> qfec_parse_opened ->
  * qfec_retire_groups -> qfec_assign_slots -> qfec_bin_arrivals ->
- * qfec_admit_ragged -> qfec_accumulate_ragged -> qfec_revive_tracked on one
- * stream, with no sync and no host decision in between; the bin reads
+ * qfec_admit_ragged -> qfec_accumulate_ragged -> qfec_revive_tracked (->
+ * qfec_record_received -> qfec_build_acks, which read hdr_out and entropy_out)
+ * on one stream, with no sync and no host decision in between; the bin reads
  * body_off_out, body_len_out, pkt_idx_out and pkt_ok.
  *
  * Inputs, n_packets records in arrival order: packet p's plaintext is
@@ -974,6 +982,158 @@ int qfec_write_private_headers(qfec_ctx* ctx, uint8_t* bytes, const uint64_t* pk
                                const uint8_t* hdr, const uint8_t* fec_offset,
                                uint64_t n_packets, int quic_version, uint64_t* body_off_out,
                                uint64_t* counts, uint32_t flags);
+
+/* Ack state on the device: QuicReceivedPacketManager and its EntropyTracker
+ * (quic_received_packet_manager.cc:40-131, :144-193, :222-286) for a whole
+ * turn.  A packet's entropy bit (qfec_parse_opened's entropy_out), the verdict
+ * that it verified and its header was accepted (hdr_out) and the fact that a
+ * packet was revived (qfec_revive_tracked's status and revived_idx) lie in
+ * device memory, and all three are for the receiver's ack.  These two calls end
+ * the turn where the reference's ends, with the ack frame's content: open ->
+ * qfec_parse_opened -> qfec_retire_groups -> qfec_assign_slots ->
+ * qfec_bin_arrivals -> qfec_admit_ragged -> qfec_accumulate_ragged ->
+ * qfec_revive_tracked -> qfec_record_received -> qfec_build_acks on one stream;
+ * the only copy back is the acks themselves.
+ *
+ * State, caller-allocated device memory, all zero = a new connection.  Per
+ * connection c < n_conns, window a power of two, 64 <= window <= 65536:
+ *   rcv_cells[c * window + (pn & (window - 1))]  one byte per packet number:
+ *     QFEC_CELL_RECEIVED (1), QFEC_CELL_ENTROPY (2, the entropy flag),
+ *     QFEC_CELL_REVIVED (4, revived at some time); a packet counts as revived
+ *     while the REVIVED bit is set and the RECEIVED bit is clear.  Cells are only OR-ed into, or
+ *     cleared when the window passes over them.  rcv_cells is 4-byte aligned.
+ *   rcv_least[c]    peer_least_packet_awaiting_ack_; below, lo = max(it, 1)
+ *   rcv_largest[c]  largest_observed
+ *   rcv_hash[c]     the cumulative entropy of everything below lo
+ * Only cells of pn in [lo, rcv_largest[c]] are live; every other cell's
+ * content is unspecified and is never read as state.  The ack's entropy hash is
+ * rcv_hash[c] ^ XOR{ e(pn) << (pn % 8) : pn live and received }.
+ *
+ * qfec_record_received: one turn into the state.  The outputs are a pure
+ * function of the inputs (no atomic order shows in them); the rule, stated
+ * sequentially, L = rcv_least[c], G = rcv_largest[c]:
+ *   1 arrivals, n_packets records in arrival order (packet_number, pkt_conn;
+ *     hdr = the parse's hdr_out, NULL: all accepted; entropy = its
+ *     entropy_out, any non-zero value is flag 1, NULL: all 0), each classified
+ *     against the state as it was BEFORE the call; first match wins and
+ *     rcv_out[p] is the class:
+ *       hdr[p] >= 0x80                     QFEC_RCV_NOT_ACCEPTED
+ *       pkt_conn[p] >= n_conns             QFEC_RCV_RANGE, latched: the next
+ *                                          qfec_sync returns
+ *                                          -QUIC_INVALID_FEC_DATA
+ *       pn == 0 or pn < L                  QFEC_RCV_STALE
+ *       pn - max(L, 1) >= window           QFEC_RCV_OVERFLOW: a result, not an
+ *                                          error; the host closes the
+ *                                          connection, as the reference does at
+ *                                          kMaxTrackedPackets
+ *       pn <= G, its cell has RECEIVED    QFEC_RCV_DUPLICATE
+ *       otherwise                          QFEC_RCV_RECORDED
+ *     Then G' = max(G, the largest RECORDED pn of c); the cells of (max(G, lo -
+ *     1), G'] are cleared; every RECORDED packet ORs 1 | flag << 1 into its
+ *     cell.  Copies of one packet inside one call are each RECORDED, and where
+ *     they disagree on the flag it stays 1.
+ *   2 revived, n_groups groups of the turn's qfec_revive_tracked (status,
+ *     revived_idx, slot -- NULL: group g has slot g -- with the assign's
+ *     slot_key and the retire's key_shift; n_groups == 0 skips the step): for
+ *     every group with status QFEC_GROUP_REVIVED and slot[g] < n_slots, key =
+ *     slot_key[slot[g]], c = key >> key_shift, pn = (key & ((1 << key_shift) -
+ *     1)) + revived_idx[g].  If key != QFEC_NO_KEY, c < n_conns, lo <= pn < G'
+ *     and the cell lacks RECEIVED, 4 is OR-ed into the cell
+ *     (RecordPacketRevived's IsMissing test in integration/libquic_fec.patch);
+ *     otherwise nothing is written and the group counts as "revived, not
+ *     missing".  The call is queued after the turn's qfec_revive_tracked and
+ *     before the next qfec_assign_slots: a released slot's slot_key names its
+ *     group until the slot is reused.
+ *   3 raises, the turn's STOP_WAITING frames (raise_conn, raise_least,
+ *     raise_hash; at most one per connection per call: the caller's guarantee,
+ *     unchecked, as the admit's distinct slots are).  For L' = raise_least[i] >
+ *     L: with L' <= G' + 1, if some pn in [lo, L') lacks RECEIVED rcv_hash =
+ *     raise_hash[i] (SetCumulativeEntropyUpTo after RemoveUpTo returned true),
+ *     else rcv_hash ^= the hashes of the pn in [lo, L') (the reference keeps its
+ *     own hash); with L' > G' + 1, a jump, rcv_hash = raise_hash[i] whatever
+ *     was received.  In both cases rcv_least = L'.  raise_conn[i] >= n_conns is
+ *     skipped and latched; L' <= L changes nothing.
+ * counts[0..11] (may be NULL), written, not added to: [0..5] the packets of
+ * classes QFEC_RCV_NOT_ACCEPTED .. QFEC_RCV_RECORDED (the class is the index;
+ * every packet in exactly one); [6] cells newly set (RECORDED less the copies
+ * inside the call); [7] revived groups recorded; [8] revived groups not
+ * missing; [9] raises applied (L' > L, jumps included); [10] raises that
+ * dropped a missing packet; [11] jumps.
+ *
+ * qfec_build_acks: GetUpdatedAckFrame for the connections ack_conn[a], a <
+ * n_acks (repeats allowed); the state is only read.  max_ranges in 1..255,
+ * max_revived in 0..255.  Per ack: if G < lo, largest_observed[a] = G,
+ * entropy_hash[a] = rcv_hash and nothing else.  Otherwise the missing packets
+ * are the pn in [lo, G) lacking RECEIVED, as maximal half-open intervals in
+ * ascending order: range_lo / range_hi under range_ptr (uint32, n_acks + 1
+ * entries), the form qfec_entropy_validate_batch reads.  With more than
+ * max_ranges intervals the lowest max_ranges are kept, largest_observed[a] =
+ * (range_lo of the first one dropped) - 1 and truncated[a] = 1: the framer's
+ * truncation (quic_framer.cc:2222-2236), counted in queue intervals; the wire
+ * writer's split into runs of at most 256 stays on the host.  entropy_hash[a] =
+ * rcv_hash ^ the hashes of the received pn in [lo, largest_observed[a]]
+ * (EntropyTracker::EntropyHash).  The revived list, rev_pn under rev_ptr, is
+ * the highest max_revived revived pn in [lo, largest_observed[a]], ascending
+ * (the patched ack writer lists the newest at or below the written largest
+ * observed).  The tables have room for n_acks * max_ranges and n_acks *
+ * max_revived entries; nothing is written past range_ptr[n_acks] and
+ * rev_ptr[n_acks].  ack_conn[a] >= n_conns gives a zero ack with no entries and
+ * is latched.
+ *
+ * Where the two differ from the reference: a turn is the reference fed the
+ * turn's accepted arrivals in arrival order, then the revived packets, then the
+ * raises; the interleaving inside a turn is gone, as qfec_retire_groups
+ * explains for groups.  Copies inside one call are both RECORDED and the flag
+ * is OR-ed (the reference lets the first copy win).  A packet with G < pn < L
+ * can only exist after a jump and is STALE here (the reference moves
+ * largest_observed and sometimes records its entropy).  A jump always adopts
+ * the frame's hash (the reference trips DCHECK_LE(packet_number,
+ * largest_observed_) there).  What stays with the host: receipt times and
+ * ack_delay_time; the reordering statistics; when to send an ack
+ * (ack_frame_updated_; HasNewMissingPackets can be read off the built ack); the
+ * wire writer.
+ * Refused on the host (nothing launched, nothing written), both calls:
+ * QFEC_PTR_HOST, QFEC_PTR_MAPPED or QFEC_ASYNC; a NULL buffer other than hdr,
+ * entropy, slot and counts (record) or rev_pn with max_revived == 0 (build)
+ * -- the tables of a count that is 0 may be NULL too; key_shift outside 1..63
+ * with n_groups > 0 (record); max_ranges outside 1..255 or max_revived above
+ * 255 (build); a window that is not a power of two in 64..65536, or rcv_cells
+ * not 4-byte aligned; a count >= 2^32, or n_acks * max(max_ranges,
+ * max_revived) >= 2^32; slot == NULL with n_slots < n_groups
+ * (QFEC_ERR_INTERNAL, in that order).  A record with n_packets, n_groups and
+ * n_raise all 0 succeeds before the buffers are looked at (counts, if given,
+ * receives twelve zeroes); a build with n_acks == 0 does too (range_ptr[0] and
+ * rev_ptr[0], where given, receive 0).  QFEC_CACHED and QFEC_SMALL_GROUPS are
+ * accepted and change nothing.  Device pointers only; the calls only queue work
+ * on the context's stream, never wait and never read anything back.  Their
+ * intermediate state lives in the context-owned scratch of qfec_revive_batch
+ * and is rebuilt by every call: 8 bytes per connection (record), 8 bytes per
+ * ack (build). */
+#define QFEC_RCV_NOT_ACCEPTED 0u /* rcv_out: hdr[p] >= 0x80 */
+#define QFEC_RCV_RANGE 1u        /* connection out of range (latched) */
+#define QFEC_RCV_STALE 2u        /* packet number 0 or below the least awaited */
+#define QFEC_RCV_OVERFLOW 3u     /* beyond the window: the host closes the connection */
+#define QFEC_RCV_DUPLICATE 4u    /* received in an earlier call */
+#define QFEC_RCV_RECORDED 5u     /* recorded */
+#define QFEC_CELL_RECEIVED 1u
+#define QFEC_CELL_ENTROPY 2u
+#define QFEC_CELL_REVIVED 4u
+int qfec_record_received(qfec_ctx* ctx, const uint64_t* packet_number, const uint32_t* pkt_conn,
+                         const uint8_t* hdr, const uint8_t* entropy, uint64_t n_packets,
+                         const uint8_t* status, const uint8_t* revived_idx, const uint32_t* slot,
+                         const uint64_t* slot_key, uint64_t n_groups, uint64_t n_slots,
+                         uint32_t key_shift, const uint32_t* raise_conn,
+                         const uint64_t* raise_least, const uint8_t* raise_hash, uint64_t n_raise,
+                         uint8_t* rcv_cells, uint64_t* rcv_least, uint64_t* rcv_largest,
+                         uint8_t* rcv_hash, uint64_t n_conns, uint32_t window, uint8_t* rcv_out,
+                         uint64_t* counts, uint32_t flags);
+int qfec_build_acks(qfec_ctx* ctx, const uint32_t* ack_conn, uint64_t n_acks,
+                    const uint8_t* rcv_cells, const uint64_t* rcv_least,
+                    const uint64_t* rcv_largest, const uint8_t* rcv_hash, uint64_t n_conns,
+                    uint32_t window, uint32_t max_ranges, uint32_t max_revived,
+                    uint64_t* largest_observed, uint8_t* entropy_hash, uint8_t* truncated,
+                    uint32_t* range_ptr, uint64_t* range_lo, uint64_t* range_hi,
+                    uint32_t* rev_ptr, uint64_t* rev_pn, uint32_t flags);
 
 /* ---- single buffer ------------------------------------------------------ */
 /* out[j] ^= in[j] for j < n (QuicFecGroupInterface::XorBuffers). */

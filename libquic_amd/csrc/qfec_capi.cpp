@@ -2600,6 +2600,153 @@ int qfec_write_private_headers(qfec_ctx* ctx, uint8_t* bytes, const uint64_t* pk
   return QFEC_OK;
 }
 
+namespace {
+
+int check_ack_window(qfec_ctx* ctx, const char* what, uint32_t window, const uint8_t* rcv_cells) {
+  if (window < qfec::kAckMinWindow || window > qfec::kAckMaxWindow || (window & (window - 1)) != 0)
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: window %u is not a power of two in [%u, %u]", what,
+                window, qfec::kAckMinWindow, qfec::kAckMaxWindow);
+  if ((reinterpret_cast<uintptr_t>(rcv_cells) & 3u) != 0)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: rcv_cells is not 4-byte aligned (a cell is set by a 32-bit atomic)", what);
+  return QFEC_OK;
+}
+
+}  // namespace
+
+// QuicReceivedPacketManager::RecordPacketReceived, RecordPacketRevived (the
+// v<=31 patch) and UpdatePacketInformationSentByPeer for a whole turn, behind
+// the revive: the parse's verdicts and entropy bits, the revive's results and
+// the turn's STOP_WAITING frames go into the caller's per-connection ack state.
+// Up to two memsets and five kernels on the stream, in the revive calls'
+// scratch; every check that needs the tables is the kernels'.
+int qfec_record_received(qfec_ctx* ctx, const uint64_t* packet_number, const uint32_t* pkt_conn,
+                         const uint8_t* hdr, const uint8_t* entropy, uint64_t n_packets,
+                         const uint8_t* status, const uint8_t* revived_idx, const uint32_t* slot,
+                         const uint64_t* slot_key, uint64_t n_groups, uint64_t n_slots,
+                         uint32_t key_shift, const uint32_t* raise_conn,
+                         const uint64_t* raise_least, const uint8_t* raise_hash, uint64_t n_raise,
+                         uint8_t* rcv_cells, uint64_t* rcv_least, uint64_t* rcv_largest,
+                         uint8_t* rcv_hash, uint64_t n_conns, uint32_t window, uint8_t* rcv_out,
+                         uint64_t* counts, uint32_t flags) {
+  const char* const what = "record received";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_device_only(ctx, what, flags))) return rc;
+  if (n_packets == 0 && n_groups == 0 && n_raise == 0)
+    return zero_counts(ctx, counts, qfec::kRecordCounts);
+  if ((n_packets != 0 && (!packet_number || !pkt_conn || !rcv_out)) ||
+      (n_groups != 0 && (!status || !revived_idx || (n_slots != 0 && !slot_key))) ||
+      (n_raise != 0 && (!raise_conn || !raise_least || !raise_hash)) ||
+      (n_conns != 0 && (!rcv_cells || !rcv_least || !rcv_largest || !rcv_hash)))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: null buffer (only hdr, entropy, slot and counts may be NULL, and the tables "
+                "of a count that is 0)", what);
+  if (n_groups != 0 && (key_shift < 1 || key_shift > 63))
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: key_shift %u outside [1, 63]", what, key_shift);
+  if ((rc = check_ack_window(ctx, what, window, rcv_cells))) return rc;
+  if (n_packets >= (1ull << 32) || n_groups >= (1ull << 32) || n_slots >= (1ull << 32) ||
+      n_raise >= (1ull << 32) || n_conns >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: 2^32 or more packets, groups, slots, raises or connections (their indices "
+                "are 32 bits)", what);
+  if (!slot && n_slots < n_groups)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: slot == NULL gives group g slot g, and there are fewer slots than groups",
+                what);
+  if ((rc = revive_scratch_acquire_bytes(ctx, qfec::record_scratch_bytes(n_conns)))) return rc;
+  qfec::RecordArgs a{};
+  a.packet_number = reinterpret_cast<const unsigned long long*>(packet_number);
+  a.pkt_conn = pkt_conn;
+  a.hdr = hdr;
+  a.entropy = entropy;
+  a.n_packets = n_packets;
+  a.status = status;
+  a.revived_idx = revived_idx;
+  a.slot = slot;
+  a.slot_key = reinterpret_cast<const unsigned long long*>(slot_key);
+  a.n_groups = (uint32_t)n_groups;
+  a.n_slots = (uint32_t)n_slots;
+  a.key_shift = n_groups != 0 ? key_shift : 1u;
+  a.raise_conn = raise_conn;
+  a.raise_least = reinterpret_cast<const unsigned long long*>(raise_least);
+  a.raise_hash = raise_hash;
+  a.n_raise = (uint32_t)n_raise;
+  a.rcv_cells = rcv_cells;
+  a.rcv_least = reinterpret_cast<unsigned long long*>(rcv_least);
+  a.rcv_largest = reinterpret_cast<unsigned long long*>(rcv_largest);
+  a.rcv_hash = rcv_hash;
+  a.n_conns = (uint32_t)n_conns;
+  a.window = window;
+  a.rcv_out = rcv_out;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.err = ctx->d_err;
+  a.ncu = ctx->ncu;
+  qfec::record_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_record_received(a, ctx->stream));
+  return revive_scratch_release(ctx);
+}
+
+// QuicReceivedPacketManager::GetUpdatedAckFrame with EntropyTracker::EntropyHash
+// and the framer's truncation, for n_acks connections: read-only on the state.
+// Three kernels on the stream, in the revive calls' scratch.
+int qfec_build_acks(qfec_ctx* ctx, const uint32_t* ack_conn, uint64_t n_acks,
+                    const uint8_t* rcv_cells, const uint64_t* rcv_least,
+                    const uint64_t* rcv_largest, const uint8_t* rcv_hash, uint64_t n_conns,
+                    uint32_t window, uint32_t max_ranges, uint32_t max_revived,
+                    uint64_t* largest_observed, uint8_t* entropy_hash, uint8_t* truncated,
+                    uint32_t* range_ptr, uint64_t* range_lo, uint64_t* range_hi,
+                    uint32_t* rev_ptr, uint64_t* rev_pn, uint32_t flags) {
+  const char* const what = "build acks";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_device_only(ctx, what, flags))) return rc;
+  if (n_acks == 0) {  // two empty tables, where they are given
+    if (range_ptr) QFEC_HIP(ctx, hipMemsetAsync(range_ptr, 0, sizeof(uint32_t), ctx->stream));
+    if (rev_ptr) QFEC_HIP(ctx, hipMemsetAsync(rev_ptr, 0, sizeof(uint32_t), ctx->stream));
+    return QFEC_OK;
+  }
+  if (!ack_conn || !largest_observed || !entropy_hash || !truncated || !range_ptr || !range_lo ||
+      !range_hi || !rev_ptr || (max_revived != 0 && !rev_pn) ||
+      (n_conns != 0 && (!rcv_cells || !rcv_least || !rcv_largest || !rcv_hash)))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: null buffer (only rev_pn with max_revived == 0, and the state of no "
+                "connection, may be NULL)", what);
+  if (max_ranges < 1 || max_ranges > 255 || max_revived > 255)
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: max_ranges %u outside [1, 255] or max_revived %u above 255", what,
+                max_ranges, max_revived);
+  if ((rc = check_ack_window(ctx, what, window, rcv_cells))) return rc;
+  if (n_conns >= (1ull << 32) || n_acks >= (1ull << 32) ||
+      n_acks * std::max(max_ranges, max_revived) >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: 2^32 or more connections, acks or table entries (range_ptr and rev_ptr are "
+                "32 bits)", what);
+  if ((rc = revive_scratch_acquire_bytes(ctx, qfec::acks_scratch_bytes(n_acks)))) return rc;
+  qfec::AcksArgs a{};
+  a.ack_conn = ack_conn;
+  a.n_acks = (uint32_t)n_acks;
+  a.rcv_cells = rcv_cells;
+  a.rcv_least = reinterpret_cast<const unsigned long long*>(rcv_least);
+  a.rcv_largest = reinterpret_cast<const unsigned long long*>(rcv_largest);
+  a.rcv_hash = rcv_hash;
+  a.n_conns = (uint32_t)n_conns;
+  a.window = window;
+  a.max_ranges = max_ranges;
+  a.max_revived = max_revived;
+  a.largest_observed = reinterpret_cast<unsigned long long*>(largest_observed);
+  a.entropy_hash = entropy_hash;
+  a.truncated = truncated;
+  a.range_ptr = range_ptr;
+  a.range_lo = reinterpret_cast<unsigned long long*>(range_lo);
+  a.range_hi = reinterpret_cast<unsigned long long*>(range_hi);
+  a.rev_ptr = rev_ptr;
+  a.rev_pn = reinterpret_cast<unsigned long long*>(rev_pn);
+  a.err = ctx->d_err;
+  a.ncu = ctx->ncu;
+  qfec::acks_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_build_acks(a, ctx->stream));
+  return revive_scratch_release(ctx);
+}
+
 // qfec_revive_accumulated with the group's K and map kept per slot, where
 // qfec_admit_ragged maintains them.
 int qfec_revive_tracked(qfec_ctx* ctx, const uint8_t* acc, uint64_t acc_stride, uint16_t* acc_len,

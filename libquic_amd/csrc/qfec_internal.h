@@ -507,6 +507,93 @@ struct WriteHeadersArgs {
 };
 hipError_t launch_write_private_headers(const WriteHeadersArgs& a, hipStream_t s);
 
+// qfec_record_received / qfec_build_acks: QuicReceivedPacketManager and its
+// EntropyTracker for a whole turn, behind the revive (rule as include/qfec.h).
+// The state is the caller's: per connection a ring of `window` one-byte cells
+// (kCellReceived | kCellEntropy | kCellRevived), the least packet awaited, the
+// largest observed and the hash of everything below the least.
+constexpr uint32_t kCellReceived = 1, kCellEntropy = 2, kCellRevived = 4;
+constexpr uint32_t kRcvNotAccepted = 0, kRcvRange = 1, kRcvStale = 2, kRcvOverflow = 3,
+                   kRcvDuplicate = 4, kRcvRecorded = 5;
+constexpr uint32_t kRecordCounts = 12;  // the six classes, then [6] cells newly set, [7] revived
+                                        // recorded, [8] revived not missing, [9] raises applied,
+                                        // [10] raises that dropped a missing packet, [11] jumps
+constexpr uint32_t kAckMinWindow = 64, kAckMaxWindow = 65536;
+// Scratch of the record, a block of record_scratch_bytes(n_conns) in the revive
+// calls' allocation: per connection the largest RECORDED packet number of the
+// call, zeroed in front of the kernels.
+struct RecordArgs {
+  const unsigned long long* packet_number;  // nullable with n_packets == 0, as pkt_conn
+  const uint32_t* pkt_conn;
+  const uint8_t* hdr;      // nullable: all accepted
+  const uint8_t* entropy;  // nullable: all 0
+  uint64_t n_packets;      // < 2^32
+  const uint8_t* status;   // the revive's outputs; nullable with n_groups == 0
+  const uint8_t* revived_idx;
+  const uint32_t* slot;  // nullable: group g has slot g
+  const unsigned long long* slot_key;
+  uint32_t n_groups;
+  uint32_t n_slots;
+  uint32_t key_shift;  // 1..63
+  const uint32_t* raise_conn;  // nullable with n_raise == 0
+  const unsigned long long* raise_least;
+  const uint8_t* raise_hash;
+  uint32_t n_raise;
+  uint8_t* rcv_cells;
+  unsigned long long* rcv_least;
+  unsigned long long* rcv_largest;
+  uint8_t* rcv_hash;
+  uint32_t n_conns;  // may be 0: every connection is out of range
+  uint32_t window;   // a power of two, kAckMinWindow .. kAckMaxWindow
+  uint8_t* rcv_out;            // nullable with n_packets == 0
+  unsigned long long* counts;  // nullable: kRecordCounts words
+  unsigned long long* seen;    // scratch: n_conns
+  uint32_t* err;
+  uint32_t ncu;
+};
+inline uint64_t record_scratch_bytes(uint64_t n_conns) { return n_conns * 8; }
+inline void record_scratch_layout(RecordArgs& a, void* block) {
+  a.seen = static_cast<unsigned long long*>(block);
+}
+// Up to two memsets and five launches on s (classify, advance, set, revived,
+// raises), ordered by the stream alone.  Not all of n_packets, n_groups and
+// n_raise are 0.
+hipError_t launch_record_received(const RecordArgs& a, hipStream_t s);
+
+// Scratch of the build, a block of acks_scratch_bytes(n_acks): per ack the
+// intervals it keeps and the revived packets at or below its largest.
+struct AcksArgs {
+  const uint32_t* ack_conn;
+  uint32_t n_acks;  // > 0, and n_acks * max(max_ranges, max_revived) < 2^32
+  const uint8_t* rcv_cells;
+  const unsigned long long* rcv_least;
+  const unsigned long long* rcv_largest;
+  const uint8_t* rcv_hash;
+  uint32_t n_conns;
+  uint32_t window;
+  uint32_t max_ranges;   // 1..255
+  uint32_t max_revived;  // 0..255
+  unsigned long long* largest_observed;
+  uint8_t* entropy_hash;
+  uint8_t* truncated;
+  uint32_t* range_ptr;  // n_acks + 1
+  unsigned long long* range_lo;
+  unsigned long long* range_hi;
+  uint32_t* rev_ptr;  // n_acks + 1
+  unsigned long long* rev_pn;  // nullable with max_revived == 0
+  uint32_t* n_rng;  // scratch: n_acks
+  uint32_t* n_rev;  // scratch: n_acks (all the revived at or below the largest, not the kept)
+  uint32_t* err;
+  uint32_t ncu;
+};
+inline uint64_t acks_scratch_bytes(uint64_t n_acks) { return n_acks * 8; }
+inline void acks_scratch_layout(AcksArgs& a, void* block) {
+  a.n_rng = static_cast<uint32_t*>(block);
+  a.n_rev = a.n_rng + a.n_acks;
+}
+// Three launches on s (count, scan, fill), ordered by the stream alone.
+hipError_t launch_build_acks(const AcksArgs& a, hipStream_t s);
+
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch
 // per batch (the launch is most of a small flush's connection-thread cost).

@@ -2152,6 +2152,352 @@ __global__ __launch_bounds__(kReviveTile) void write_headers_kernel(WriteHeaders
   }
 }
 
+// ---------------------------------------------------------------------------
+// Ack state on the device (qfec_record_received, qfec_build_acks):
+// QuicReceivedPacketManager and its EntropyTracker over a turn, behind the
+// revive.
+// ---------------------------------------------------------------------------
+// The record, behind a memset of counts and of the per-connection maxima:
+//   classify : one lane per packet against the state as the call found it;
+//              rcv_out, six tallies, a 64-bit atomicMax of every RECORDED
+//              number into its connection's word of the scratch;
+//   advance  : one lane per connection; where the maximum passed the largest
+//              observed, the wave clears the cells the ring now takes in (a
+//              lane's range broadcast, 64 byte stores a trip) and the largest
+//              becomes the maximum.  No other pass stores a cell's byte;
+//   set      : one lane per packet, RECORDED ones OR received | flag << 1 into
+//              their cell by a 32-bit atomic on the word that holds it; the
+//              cell was new where the word that came back lacked the bit;
+//   revived  : one lane per group, 4 OR-ed into the cell of a revived packet
+//              that is live, below the largest and not received;
+//   raises   : one wave per STOP_WAITING over the cells the raise drops.
+// An OR and a maximum do not depend on the order of their operands, and no two
+// raises name one connection, so the atomics show nowhere.  The build is three
+// launches: one wave per ack over its live cells that counts (and writes the
+// ack's scalars), one workgroup that scans the counts into the two CSR
+// pointers, and the walk again that fills the tables.  Every connection index
+// is checked against n_conns before it indexes the state, every ring index is
+// masked with window - 1, a walk is at most window cells long whatever the
+// state holds, and a table entry is stored only below max_ranges or
+// max_revived of its ack.  All variable shifts are 32-bit (the gfx950 64-bit
+// shift hazard); keys are split in halves as retire_split does it.
+__device__ __forceinline__ uint64_t ack_cell_index(uint32_t conn, uint32_t window, uint32_t pn_lo) {
+  return (uint64_t)conn * window + (pn_lo & (window - 1u));
+}
+
+__global__ __launch_bounds__(kReviveTile) void record_classify_kernel(RecordArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves * 6];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t n[6] = {0, 0, 0, 0, 0, 0};  // the wave's packets per class (uniform)
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const uint64_t pc = in ? p : a.n_packets - 1u;  // (clamped, not masked)
+    const unsigned long long pn = a.packet_number[pc];
+    const uint32_t conn = a.pkt_conn[pc];
+    const uint32_t h = a.hdr ? a.hdr[pc] : 0u;
+    const bool known = conn < a.n_conns;
+    const uint32_t cc = known ? conn : 0u;  // (clamped; nothing to load with no connection)
+    unsigned long long least = 0, largest = 0;
+    uint32_t cell = 0;
+    if (a.n_conns != 0u) {
+      least = a.rcv_least[cc];
+      largest = a.rcv_largest[cc];
+      cell = a.rcv_cells[ack_cell_index(cc, a.window, (uint32_t)pn)];
+    }
+    const unsigned long long lo = least ? least : 1ull;
+    uint32_t cls;
+    if (h >= kHdrFailed) cls = kRcvNotAccepted;
+    else if (!known) cls = kRcvRange;
+    else if (pn == 0ull || pn < least) cls = kRcvStale;
+    else if (pn - lo >= a.window) cls = kRcvOverflow;
+    else if (pn <= largest && (cell & kCellReceived) != 0u) cls = kRcvDuplicate;
+    else cls = kRcvRecorded;
+    if (in) {
+      a.rcv_out[p] = (uint8_t)cls;
+      if (cls == kRcvRecorded) retire_max(&a.seen[conn], pn);
+    }
+#pragma unroll
+    for (uint32_t c = 0; c < 6u; ++c) n[c] += (uint32_t)__popcll(__ballot(in && cls == c));
+  }
+  const uint32_t t = block_sum(n, lane, wave, s_w);
+  if (tid < 6u && t != 0u) {
+    if (a.counts) atomicAdd(&a.counts[tid], (unsigned long long)t);
+    if (tid == kRcvRange) atomicOr(a.err, kErrMissingIndex);
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void record_advance_kernel(RecordArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t c0 = (uint64_t)blockIdx.x * kReviveTile; c0 < a.n_conns; c0 += step) {
+    const uint64_t c = c0 + threadIdx.x;
+    const bool in = c < a.n_conns;
+    const uint32_t cc = (uint32_t)(in ? c : a.n_conns - 1u);  // (clamped, not masked)
+    const unsigned long long largest = a.rcv_largest[cc], seen = a.seen[cc],
+                             least = a.rcv_least[cc];
+    const unsigned long long lo = least ? least : 1ull;
+    const bool moved = in && seen > largest;
+    // the cells of (max(largest, lo - 1), seen]: at most window, seen being RECORDED
+    const unsigned long long from = (largest >= lo ? largest : lo - 1u) + 1u;
+    const uint32_t cnt =
+        moved && seen >= from ? (uint32_t)min(seen - from + 1u, (unsigned long long)a.window) : 0u;
+    if (moved) a.rcv_largest[cc] = seen;
+    // (the ballot is the wave's: the loop and every lane_read in it are uniform)
+    for (uint64_t m = __ballot(cnt != 0u); m != 0ull; m &= m - 1ull) {
+      const uint32_t src = (uint32_t)__builtin_ctzll(m);
+      const uint32_t c_s = lane_read(cc, src), f_s = lane_read((uint32_t)from, src),
+                     n_s = lane_read(cnt, src);
+      for (uint32_t j = lane; j < n_s; j += 64u)
+        a.rcv_cells[ack_cell_index(c_s, a.window, f_s + j)] = 0;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void record_set_kernel(RecordArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t n_new = 0;  // the wave's cells newly set (uniform)
+  uint32_t* const words = reinterpret_cast<uint32_t*>(a.rcv_cells);
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const uint64_t pc = in ? p : a.n_packets - 1u;  // (clamped, not masked)
+    const uint32_t pn_lo = (uint32_t)a.packet_number[pc], conn = a.pkt_conn[pc];
+    const uint32_t flag = a.entropy ? (uint32_t)(a.entropy[pc] != 0) : 0u;
+    bool fresh = false;
+    if (in && a.rcv_out[pc] == kRcvRecorded) {  // (RECORDED: conn < n_conns)
+      const uint64_t idx = ack_cell_index(conn, a.window, pn_lo);
+      const uint32_t sh = ((uint32_t)idx & 3u) * 8u;
+      const uint32_t old = atomicOr(&words[idx >> 2], (kCellReceived | flag << 1) << sh);
+      fresh = ((old >> sh) & kCellReceived) == 0u;
+    }
+    n_new += (uint32_t)__popcll(__ballot(fresh));
+  }
+  const uint32_t t = block_sum(n_new, lane, wave, s_w);
+  if (tid == 0u && t != 0u && a.counts) atomicAdd(&a.counts[6], (unsigned long long)t);
+}
+
+// key >> sh and key & ((1 << sh) - 1) in 32-bit halves, sh in 1..63
+__device__ __forceinline__ void ack_split_key(unsigned long long key, uint32_t sh, uint32_t& c_lo,
+                                              uint32_t& c_hi, unsigned long long& number) {
+  const uint32_t lo = (uint32_t)key, hi = (uint32_t)(key >> 32);
+  uint32_t n_lo, n_hi;
+  if (sh >= 32u) {
+    const uint32_t t = sh - 32u;  // 0 .. 31
+    c_lo = hi >> t;
+    c_hi = 0u;
+    n_lo = lo;
+    n_hi = hi & ((1u << t) - 1u);
+  } else {  // 1 .. 31
+    c_lo = (lo >> sh) | (hi << (32u - sh));
+    c_hi = hi >> sh;
+    n_lo = lo & ((1u << sh) - 1u);
+    n_hi = 0u;
+  }
+  number = (unsigned long long)n_lo | ((unsigned long long)n_hi << 32);
+}
+
+__global__ __launch_bounds__(kReviveTile) void record_revived_kernel(RecordArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves * 2];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t n[2] = {0, 0};  // the wave's revived groups (uniform): recorded, not missing
+  uint32_t* const words = reinterpret_cast<uint32_t*>(a.rcv_cells);
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t g0 = (uint64_t)blockIdx.x * kReviveTile; g0 < a.n_groups; g0 += step) {
+    const uint64_t g = g0 + tid;
+    const bool in = g < a.n_groups;
+    const uint64_t gc = in ? g : a.n_groups - 1u;  // (clamped, not masked)
+    const uint32_t st = a.status[gc], ri = a.revived_idx[gc];
+    const uint32_t s = a.slot ? a.slot[gc] : (uint32_t)gc;
+    const bool cand = in && st == 1u /* QFEC_GROUP_REVIVED */ && s < a.n_slots;
+    unsigned long long key = kAssignNoKey;
+    if (a.n_slots != 0u) key = a.slot_key[s < a.n_slots ? s : 0u];  // (clamped)
+    uint32_t c_lo, c_hi;
+    unsigned long long first;
+    ack_split_key(key, a.key_shift, c_lo, c_hi, first);
+    const bool known = key != kAssignNoKey && c_hi == 0u && c_lo < a.n_conns;
+    const uint32_t cc = known ? c_lo : 0u;  // (clamped)
+    const unsigned long long pn = first + ri;
+    unsigned long long least = 0, largest = 0;
+    uint32_t cell = 0;
+    if (a.n_conns != 0u) {
+      least = a.rcv_least[cc];
+      largest = a.rcv_largest[cc];
+      cell = a.rcv_cells[ack_cell_index(cc, a.window, (uint32_t)pn)];
+    }
+    const unsigned long long lo = least ? least : 1ull;
+    // RecordPacketRevived's IsMissing; (largest - lo < window: the index is the cell's)
+    const bool missing =
+        cand && known && pn >= lo && pn < largest && (cell & kCellReceived) == 0u;
+    if (missing) {
+      const uint64_t idx = ack_cell_index(cc, a.window, (uint32_t)pn);
+      atomicOr(&words[idx >> 2], kCellRevived << (((uint32_t)idx & 3u) * 8u));
+    }
+    n[0] += (uint32_t)__popcll(__ballot(missing));
+    n[1] += (uint32_t)__popcll(__ballot(cand && !missing));
+  }
+  const uint32_t t = block_sum(n, lane, wave, s_w);
+  if (tid < 2u && t != 0u && a.counts) atomicAdd(&a.counts[7u + tid], (unsigned long long)t);
+}
+
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d);
+  return v;
+}
+
+// One wave per raise (no two of a call name one connection: the caller's).
+__global__ __launch_bounds__(kReviveTile) void record_raise_kernel(RecordArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves * 4];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t n[4] = {0, 0, 0, 0};  // the wave's raises (uniform): applied, dropped one, jumps, range
+  const uint64_t step = (uint64_t)gridDim.x * kTurnWaves;
+  for (uint64_t i = (uint64_t)blockIdx.x * kTurnWaves + wave; i < a.n_raise; i += step) {
+    const uint32_t conn = a.raise_conn[i];
+    const unsigned long long up = a.raise_least[i];
+    const uint32_t frame_hash = a.raise_hash[i];
+    if (conn >= a.n_conns) {
+      ++n[3];
+      continue;
+    }
+    const unsigned long long least = a.rcv_least[conn], largest = a.rcv_largest[conn];
+    if (up <= least) continue;
+    ++n[0];
+    uint32_t hash = frame_hash;
+    if (up > largest + 1u) {
+      ++n[2];  // a jump: nothing of the ring is left below it
+    } else {
+      const unsigned long long lo = least ? least : 1ull;
+      const uint32_t len = (uint32_t)min(up - lo, (unsigned long long)a.window), lo32 = (uint32_t)lo;
+      uint32_t x = 0, gone = 0;
+      for (uint32_t j0 = 0; j0 < len; j0 += 64u) {
+        const uint32_t j = j0 + lane;
+        const uint32_t jc = j < len ? j : len - 1u;  // (clamped, not masked)
+        const uint32_t cell = a.rcv_cells[ack_cell_index(conn, a.window, lo32 + jc)];
+        const bool got = (cell & kCellReceived) != 0u;
+        if (j < len && got) x ^= ((cell >> 1) & 1u) << ((lo32 + j) & 7u);
+        if (j < len && !got) gone = 1u;
+      }
+      x = wave_xor(x);
+      const bool lost = __ballot(gone != 0u) != 0ull;
+      if (lost) ++n[1];
+      else hash = (uint32_t)a.rcv_hash[conn] ^ x;
+    }
+    if (lane == 0u) {
+      a.rcv_hash[conn] = (uint8_t)hash;
+      a.rcv_least[conn] = up;
+    }
+  }
+  const uint32_t t = block_sum(n, lane, wave, s_w);
+  if (tid < 4u && t != 0u) {
+    if (tid < 3u && a.counts) atomicAdd(&a.counts[9u + tid], (unsigned long long)t);
+    if (tid == 3u) atomicOr(a.err, kErrMissingIndex);
+  }
+}
+
+// One ack's walk over its live cells, by one wave.  FILL == false: the ack's
+// scalars and its two counts; FILL == true: the same walk again, the tables.
+template <bool FILL>
+__device__ __forceinline__ void ack_walk(const AcksArgs& a, uint64_t i, uint32_t lane) {
+  const uint32_t conn = a.ack_conn[i];
+  unsigned long long least = 0, largest = 0;
+  uint32_t hash = 0;
+  const bool known = conn < a.n_conns;  // (uniform, as everything read per ack)
+  if (known) {
+    least = a.rcv_least[conn];
+    largest = a.rcv_largest[conn];
+    hash = a.rcv_hash[conn];
+  }
+  const unsigned long long lo = least ? least : 1ull;
+  uint32_t kept = 0, n_revd = 0, cut = 0;
+  if (known && largest >= lo) {
+    const uint32_t len = (uint32_t)min(largest - lo + 1u, (unsigned long long)a.window),
+                   lo32 = (uint32_t)lo;
+    uint32_t rp = 0, vp = 0, keep_from = 0;
+    if (FILL) {
+      rp = a.range_ptr[i];
+      vp = a.rev_ptr[i];
+      const uint32_t all = a.n_rev[i];
+      keep_from = all - min(all, a.max_revived);
+    }
+    uint32_t n_start = 0, x = 0, carry = 0;  // (carry: the cell below this trip's was missing)
+    for (uint32_t j0 = 0; j0 < len && cut == 0u; j0 += 64u) {
+      const uint32_t j = j0 + lane;
+      const bool inr = j < len;
+      const uint32_t jc = inr ? j : len - 1u;  // (clamped, not masked)
+      const uint32_t cell = a.rcv_cells[ack_cell_index(conn, a.window, lo32 + jc)];
+      const uint32_t miss = (uint32_t)(inr && (cell & kCellReceived) == 0u);
+      // (every lane shuffles before anything is compared)
+      const uint32_t below = lane_read(miss, lane ? lane - 1u : 0u);
+      const uint32_t last = lane_read(miss, 63u);
+      const bool prev = (lane ? below : carry) != 0u;
+      const bool start = miss != 0u && !prev, end = inr && miss == 0u && prev;
+      const uint64_t bs = __ballot(start);
+      const uint32_t sidx = n_start + ballot_rank(bs);  // starts below this cell
+      // the first interval that does not fit cuts the ack off below its first packet
+      const uint64_t bt = __ballot(start && sidx == a.max_ranges);
+      uint32_t lim = len;
+      if (bt != 0ull) {
+        cut = 1u;
+        lim = j0 + (uint32_t)__builtin_ctzll(bt);
+        largest = lo + lim - 1u;
+      }
+      const bool live = j < lim;
+      if (live && miss == 0u) x ^= ((cell >> 1) & 1u) << ((lo32 + j) & 7u);
+      const bool revd = live && miss != 0u && (cell & kCellRevived) != 0u;
+      const uint64_t br = __ballot(revd);
+      const uint32_t ridx = n_revd + ballot_rank(br);
+      if (FILL) {
+        if (start && sidx < a.max_ranges) a.range_lo[(uint64_t)rp + sidx] = lo + j;
+        if (end && sidx != 0u && sidx - 1u < a.max_ranges)
+          a.range_hi[(uint64_t)rp + sidx - 1u] = lo + j;
+        if (revd && ridx >= keep_from && ridx - keep_from < a.max_revived)
+          a.rev_pn[(uint64_t)vp + ridx - keep_from] = lo + j;
+      }
+      n_start += (uint32_t)__popcll(bs);
+      n_revd += (uint32_t)__popcll(br);
+      carry = last;
+    }
+    kept = min(n_start, a.max_ranges);
+    hash ^= wave_xor(x);
+  }
+  if (!FILL && lane == 0u) {
+    a.largest_observed[i] = largest;
+    a.entropy_hash[i] = (uint8_t)hash;
+    a.truncated[i] = (uint8_t)cut;
+    a.n_rng[i] = kept;
+    a.n_rev[i] = n_revd;
+    if (!known) atomicOr(a.err, kErrMissingIndex);
+  }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(kReviveTile) void acks_walk_kernel(AcksArgs a) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint64_t step = (uint64_t)gridDim.x * kTurnWaves;
+  for (uint64_t i = (uint64_t)blockIdx.x * kTurnWaves + wave; i < a.n_acks; i += step)
+    ack_walk<FILL>(a, i, lane);
+}
+
+// One workgroup: the two CSR pointers from the per-ack counts.  The sums fit
+// 32 bits: n_acks * max(max_ranges, max_revived) < 2^32.
+__global__ __launch_bounds__(kRvScanBlock) void acks_scan_kernel(AcksArgs a) {
+  __shared__ uint32_t s_w[kRvScanBlock / 64];
+  const uint64_t rng = tile_scan(
+      a.n_acks, s_w, [=](uint64_t i) { return a.n_rng[i]; },
+      [=](uint64_t i, uint64_t x) { a.range_ptr[i] = (uint32_t)x; });
+  const uint64_t rev = tile_scan(
+      a.n_acks, s_w, [=](uint64_t i) { return min(a.n_rev[i], a.max_revived); },
+      [=](uint64_t i, uint64_t x) { a.rev_ptr[i] = (uint32_t)x; });
+  if (threadIdx.x == 0u) {
+    a.range_ptr[a.n_acks] = (uint32_t)rng;
+    a.rev_ptr[a.n_acks] = (uint32_t)rev;
+  }
+}
+
 // The recover body over the work list, L >= 16: lanes, windows and loads as
 // fixed_xor_kernel; workgroup step i takes entries [i * gpb, (i + 1) * gpb).
 // `work` and `totals` are separate restrict parameters so that their loads
@@ -4614,6 +4960,36 @@ hipError_t launch_write_private_headers(const WriteHeadersArgs& a, hipStream_t s
   if (a.n_packets == 0) return hipSuccess;
   hipError_t e = a.counts ? hipMemsetAsync(a.counts, 0, 2 * sizeof(uint64_t), s) : hipSuccess;
   return launch_pass(e, write_headers_kernel, per_packet_grid(a.n_packets, a.ncu), kReviveTile, s, a);
+}
+
+hipError_t launch_record_received(const RecordArgs& a, hipStream_t s) {
+  if (a.n_packets == 0 && a.n_groups == 0 && a.n_raise == 0) return hipSuccess;
+  hipError_t e =
+      a.counts ? hipMemsetAsync(a.counts, 0, kRecordCounts * sizeof(uint64_t), s) : hipSuccess;
+  if (a.n_packets != 0) {
+    const uint32_t pgrid = per_packet_grid(a.n_packets, a.ncu);
+    if (e == hipSuccess && a.n_conns != 0)
+      e = hipMemsetAsync(a.seen, 0, record_scratch_bytes(a.n_conns), s);
+    e = launch_pass(e, record_classify_kernel, pgrid, kReviveTile, s, a);
+    if (a.n_conns != 0) {  // (else nothing was RECORDED)
+      e = launch_pass(e, record_advance_kernel, per_packet_grid(a.n_conns, a.ncu), kReviveTile, s, a);
+      e = launch_pass(e, record_set_kernel, pgrid, kReviveTile, s, a);
+    }
+  }
+  if (a.n_groups != 0)
+    e = launch_pass(e, record_revived_kernel, per_packet_grid(a.n_groups, a.ncu), kReviveTile, s, a);
+  if (a.n_raise != 0)  // (a wave per raise)
+    e = launch_pass(e, record_raise_kernel, per_packet_grid((uint64_t)a.n_raise * 64u, a.ncu),
+                    kReviveTile, s, a);
+  return e;
+}
+
+hipError_t launch_build_acks(const AcksArgs& a, hipStream_t s) {
+  if (a.n_acks == 0) return hipSuccess;
+  const uint32_t wgrid = per_packet_grid((uint64_t)a.n_acks * 64u, a.ncu);  // (a wave per ack)
+  hipError_t e = launch_pass(hipSuccess, acks_walk_kernel<false>, wgrid, kReviveTile, s, a);
+  e = launch_pass(e, acks_scan_kernel, 1, kRvScanBlock, s, a);
+  return launch_pass(e, acks_walk_kernel<true>, wgrid, kReviveTile, s, a);
 }
 
 hipError_t launch_accumulate_ragged(const AccumulateRaggedArgs& a0, hipStream_t s) {

@@ -46,6 +46,15 @@ QFEC_HDR_NO_OFFSET = 0x83
 QFEC_HDR_BAD_OFFSET = 0x84
 QFEC_HDR_RANGE = 0x85
 QFEC_HDR_EMPTY = 0x86
+QFEC_RCV_NOT_ACCEPTED = 0
+QFEC_RCV_RANGE = 1
+QFEC_RCV_STALE = 2
+QFEC_RCV_OVERFLOW = 3
+QFEC_RCV_DUPLICATE = 4
+QFEC_RCV_RECORDED = 5
+QFEC_CELL_RECEIVED = 1
+QFEC_CELL_ENTROPY = 2
+QFEC_CELL_REVIVED = 4
 MAX_PACKET_SIZE = 1452
 DEFAULT_MAX_PACKET_SIZE = 1350
 MAX_GROUP_PACKETS = 255
@@ -121,6 +130,13 @@ SIGNATURES = [
       _u8p, _u8p, _vp, C.c_uint32]),
     ("qfec_write_private_headers", C.c_int,
      [_vp, _u8p, _vp, _u8p, _u8p, C.c_uint64, C.c_int, _vp, _vp, C.c_uint32]),
+    ("qfec_record_received", C.c_int,
+     [_vp, _vp, _vp, _u8p, _u8p, C.c_uint64, _u8p, _u8p, _vp, _vp, C.c_uint64, C.c_uint64,
+      C.c_uint32, _vp, _vp, _u8p, C.c_uint64, _u8p, _vp, _vp, _u8p, C.c_uint64, C.c_uint32, _u8p,
+      _vp, C.c_uint32]),
+    ("qfec_build_acks", C.c_int,
+     [_vp, _vp, C.c_uint64, _u8p, _vp, _vp, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+      _vp, _u8p, _u8p, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
     ("qfec_xor_into", C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint32]),
     ("qfec_wire_write_private_header", C.c_size_t, [_vp, _u8p, C.c_size_t]),
     ("qfec_wire_parse_private_header", C.c_size_t,
@@ -695,6 +711,58 @@ class Context:
         rc = self.lib.qfec_write_private_headers(self.ctx, _ptr(data), _ptr(pkt_off), _ptr(hdr),
                                                  _ptr(fec_offset), n_packets, quic_version,
                                                  _ptr(body_off_out), _ptr(counts), flags)
+        return self._check(rc)
+
+    def record_received(self, rcv_cells, rcv_least, rcv_largest, rcv_hash, n_conns, window, *,
+                        packet_number=None, pkt_conn=None, n_packets=0, rcv_out=None, hdr=None,
+                        entropy=None, status=None, revived_idx=None, slot=None, slot_key=None,
+                        n_groups=0, n_slots=0, key_shift=0, raise_conn=None, raise_least=None,
+                        raise_hash=None, n_raise=0, counts=None, flags=0):
+        """qfec_record_received, behind revive_tracked: one turn into the ack
+        state.  The state is the caller's, all zero for a new connection:
+        rcv_cells (uint8[n_conns * window], window a power of two in 64..65536;
+        the cell of packet pn is pn & (window - 1): QFEC_CELL_RECEIVED |
+        QFEC_CELL_ENTROPY | QFEC_CELL_REVIVED), rcv_least and rcv_largest
+        (uint64[n_conns]), rcv_hash (uint8[n_conns]).  Arrivals: packet_number
+        (uint64), pkt_conn (uint32), hdr (uint8, optional: parse_opened's
+        hdr_out, accepted below 0x80), entropy (uint8, optional: its
+        entropy_out, non-zero = flag 1); rcv_out (uint8[n_packets]) gets a
+        QFEC_RCV_* class per packet.  Revived: revive_tracked's status,
+        revived_idx and slot with assign_slots' slot_key (uint64[n_slots]) and
+        retire_groups' key_shift.  Raises: the turn's STOP_WAITING frames,
+        raise_conn (uint32, at most one per connection), raise_least (uint64),
+        raise_hash (uint8).  counts (uint64[12], optional): the six classes,
+        cells newly set, revived recorded, revived not missing, raises
+        applied, raises that dropped a missing packet, jumps.  Device pointers
+        only; queued on the context's stream (sync() before reading)."""
+        rc = self.lib.qfec_record_received(
+            self.ctx, _ptr(packet_number), _ptr(pkt_conn), _ptr(hdr), _ptr(entropy), n_packets,
+            _ptr(status), _ptr(revived_idx), _ptr(slot), _ptr(slot_key), n_groups, n_slots,
+            key_shift, _ptr(raise_conn), _ptr(raise_least), _ptr(raise_hash), n_raise,
+            _ptr(rcv_cells), _ptr(rcv_least), _ptr(rcv_largest), _ptr(rcv_hash), n_conns, window,
+            _ptr(rcv_out), _ptr(counts), flags)
+        return self._check(rc)
+
+    def build_acks(self, ack_conn, n_acks, rcv_cells, rcv_least, rcv_largest, rcv_hash, n_conns,
+                   window, max_ranges, max_revived, largest_observed, entropy_hash, truncated,
+                   range_ptr, range_lo, range_hi, rev_ptr, rev_pn=None, *, flags=0):
+        """qfec_build_acks: the ack frame's content for the connections
+        ack_conn (uint32[n_acks], repeats allowed) from the state
+        record_received keeps; the state is only read.  largest_observed
+        (uint64), entropy_hash and truncated (uint8) per ack; the missing
+        packets as ascending half-open intervals range_lo / range_hi (uint64,
+        room for n_acks * max_ranges) under range_ptr (uint32[n_acks + 1]),
+        the form entropy_validate reads; the revived packets rev_pn (uint64,
+        room for n_acks * max_revived) under rev_ptr.  With more than
+        max_ranges (1..255) intervals the lowest are kept, largest_observed
+        falls to just below the first one dropped and truncated is 1.  Device
+        pointers only; queued on the context's stream (sync() before
+        reading)."""
+        rc = self.lib.qfec_build_acks(
+            self.ctx, _ptr(ack_conn), n_acks, _ptr(rcv_cells), _ptr(rcv_least), _ptr(rcv_largest),
+            _ptr(rcv_hash), n_conns, window, max_ranges, max_revived, _ptr(largest_observed),
+            _ptr(entropy_hash), _ptr(truncated), _ptr(range_ptr), _ptr(range_lo), _ptr(range_hi),
+            _ptr(rev_ptr), _ptr(rev_pn), flags)
         return self._check(rc)
 
     def xor_into(self, src, n, dst, *, host=False, mapped=False):
