@@ -54,6 +54,10 @@
  *       UpdatePacketInformationSentByPeer; GetUpdatedAckFrame and EntropyHash),
  *       for a whole turn behind the revive: the parse's verdicts and entropy
  *       bits and the revive's results become the ack frames' content.
+ *   qfec_write_ack_frames
+ *       is QuicFramer::AppendAckFrameAndTypeByte (v<=31, with the patch's
+ *       revived tail) over the built acks: the frames' wire bytes, where the
+ *       seal reads them.
  *   qfec_recover_batch / _strided / qfec_recover_ragged
  *       replaces QuicFecGroup::UpdateFec + Update(received) + CanRevive() +
  *       Revive().  Receive-side hook: QuicConnection::ProcessValidatedPacket
@@ -789,7 +793,7 @@ int qfec_assign_slots(qfec_ctx* ctx, const uint64_t* pkt_key, const uint8_t* pkt
  * front of the assign: the turn is open -> qfec_retire_groups ->
  * qfec_assign_slots -> qfec_bin_arrivals -> qfec_admit_ragged ->
  * qfec_accumulate_ragged -> qfec_revive_tracked (-> qfec_record_received ->
- * qfec_build_acks, below) on one stream, with no sync and
+ * qfec_build_acks -> qfec_write_ack_frames, below) on one stream, with no sync and
  * no host decision in between.  Per packet the host supplies what the header
  * gives, per connection only the STOP_WAITING thresholds of the turn.
  *
@@ -992,8 +996,9 @@ int qfec_write_private_headers(qfec_ctx* ctx, uint8_t* bytes, const uint64_t* pk
  * the turn where the reference's ends, with the ack frame's content: open ->
  * qfec_parse_opened -> qfec_retire_groups -> qfec_assign_slots ->
  * qfec_bin_arrivals -> qfec_admit_ragged -> qfec_accumulate_ragged ->
- * qfec_revive_tracked -> qfec_record_received -> qfec_build_acks on one stream;
- * the only copy back is the acks themselves.
+ * qfec_revive_tracked -> qfec_record_received -> qfec_build_acks ->
+ * qfec_write_ack_frames on one stream, and the frames go to the seal where they
+ * lie; the only copy back is the sealed ack packets.
  *
  * State, caller-allocated device memory, all zero = a new connection.  Per
  * connection c < n_conns, window a power of two, 64 <= window <= 65536:
@@ -1070,7 +1075,7 @@ int qfec_write_private_headers(qfec_ctx* ctx, uint8_t* bytes, const uint64_t* pk
  * max_ranges intervals the lowest max_ranges are kept, largest_observed[a] =
  * (range_lo of the first one dropped) - 1 and truncated[a] = 1: the framer's
  * truncation (quic_framer.cc:2222-2236), counted in queue intervals; the wire
- * writer's split into runs of at most 256 stays on the host.  entropy_hash[a] =
+ * writer's split into runs of at most 256 is qfec_write_ack_frames'.  entropy_hash[a] =
  * rcv_hash ^ the hashes of the received pn in [lo, largest_observed[a]]
  * (EntropyTracker::EntropyHash).  The revived list, rev_pn under rev_ptr, is
  * the highest max_revived revived pn in [lo, largest_observed[a]], ascending
@@ -1090,8 +1095,9 @@ int qfec_write_private_headers(qfec_ctx* ctx, uint8_t* bytes, const uint64_t* pk
  * the frame's hash (the reference trips DCHECK_LE(packet_number,
  * largest_observed_) there).  What stays with the host: receipt times and
  * ack_delay_time; the reordering statistics; when to send an ack
- * (ack_frame_updated_; HasNewMissingPackets can be read off the built ack); the
- * wire writer.
+ * (ack_frame_updated_; HasNewMissingPackets can be read off the built ack).  The
+ * wire writer is qfec_write_ack_frames; the frame's timestamp block stays with
+ * the receipt times, on the host.
  * Refused on the host (nothing launched, nothing written), both calls:
  * QFEC_PTR_HOST, QFEC_PTR_MAPPED or QFEC_ASYNC; a NULL buffer other than hdr,
  * entropy, slot and counts (record) or rev_pn with max_revived == 0 (build)
@@ -1135,6 +1141,59 @@ int qfec_build_acks(qfec_ctx* ctx, const uint32_t* ack_conn, uint64_t n_acks,
                     uint32_t* range_ptr, uint64_t* range_lo, uint64_t* range_hi,
                     uint32_t* rev_ptr, uint64_t* rev_pn, uint32_t flags);
 
+/* qfec_write_ack_frames: the built acks as v<=31 ack frames, the bytes of
+ * QuicFramer::AppendAckFrameAndTypeByte (quic_framer.cc:2172-2320, GetAckFrameInfo
+ * :1005-1033) with the revived tail of integration/libquic_fec.patch -- the rule
+ * is qfec_wire_write_ack_frame's, below, and the turn ends build -> write -> seal
+ * on one stream, with one copy back of finished packets.  Inputs: ack_conn and
+ * the eight outputs of qfec_build_acks (rev_pn may be NULL where rev_ptr lists
+ * nothing); ack_delay_us[a] in microseconds, UINT64_MAX or a NULL array:
+ * infinite; the ring rcv_cells with window and n_conns, only read.  Ack a's
+ * frame goes to out + out_off[a] (any alignment) and has out_cap[a] bytes of
+ * room there, the writer's capacity at the frame's first byte.  Every interval
+ * is split into nack ranges of at most 256 numbers; with more of them than the
+ * room holds the writer cuts the ack as the framer does: the lowest ranges that
+ * fit are kept, the largest observed written is (first range dropped) - 1, and
+ * the hash is entropy_hash[a] ^ the hashes of the received numbers in (largest
+ * written, largest_observed[a]], read from the cells' QFEC_CELL_ENTROPY bits.
+ * An ack with truncated[a] set is written as the frame it is (its lengths and
+ * largest gap taken from the intervals given, the truncated bit set, no
+ * timestamp byte) and may be cut further.  The timestamp count of a frame that
+ * is not truncated is 0: receipt times stay with the host.
+ * Outputs: out_len[a] = prefix_len + the frame's length, or 0 where nothing was
+ * written -- with in_off[a] = out_off[a] - prefix_len (the packet header and
+ * private flags in front of the frame) the seal calls take it as their in_len;
+ * wire_largest[a] and wire_hash[a], the two as written (as given where nothing
+ * was); ack_status[a]; counts[0..3] (may be NULL), written, not added to: the
+ * acks per status.  ack_conn[a] >= n_conns gives length 0 and QFEC_ACKW_RANGE
+ * and is latched, as in the build.  The tables are the caller's guarantee;
+ * whatever they hold, no byte is stored outside [out_off[a], out_off[a] +
+ * out_cap[a]), no cell is read outside the ring, at most 255 intervals and 255
+ * revived numbers of an ack are read and every walk over cells is at most
+ * window long.
+ * Refused on the host (nothing launched, nothing written), in this order:
+ * QFEC_PTR_HOST, QFEC_PTR_MAPPED or QFEC_ASYNC; a NULL buffer other than
+ * ack_delay_us, rev_pn and counts (rcv_cells may be NULL with n_conns == 0); a
+ * window that is not a power of two in 64..65536 or rcv_cells not 4-byte
+ * aligned; n_acks or n_conns >= 2^32; prefix_len > 64 (QFEC_ERR_INTERNAL).
+ * n_acks == 0 succeeds before the buffers are looked at (counts, if given,
+ * receives four zeroes).  One kernel on the context's stream, no scratch; the
+ * call never waits and never reads anything back. */
+#define QFEC_ACKW_WRITTEN 0u /* ack_status: the frame holds all that was given */
+#define QFEC_ACKW_CUT 1u     /* written, cut further by the writer */
+#define QFEC_ACKW_NO_ROOM 2u /* no room for a mandatory byte: nothing written */
+#define QFEC_ACKW_RANGE 3u   /* connection out of range (latched): nothing written */
+int qfec_write_ack_frames(qfec_ctx* ctx, const uint32_t* ack_conn, uint64_t n_acks,
+                          const uint64_t* largest_observed, const uint8_t* entropy_hash,
+                          const uint8_t* truncated, const uint32_t* range_ptr,
+                          const uint64_t* range_lo, const uint64_t* range_hi,
+                          const uint32_t* rev_ptr, const uint64_t* rev_pn,
+                          const uint64_t* ack_delay_us, const uint8_t* rcv_cells,
+                          uint64_t n_conns, uint32_t window, uint8_t* out,
+                          const uint64_t* out_off, const uint16_t* out_cap, uint32_t prefix_len,
+                          uint16_t* out_len, uint64_t* wire_largest, uint8_t* wire_hash,
+                          uint8_t* ack_status, uint64_t* counts, uint32_t flags);
+
 /* ---- single buffer ------------------------------------------------------ */
 /* out[j] ^= in[j] for j < n (QuicFecGroupInterface::XorBuffers). */
 int qfec_xor_into(qfec_ctx* ctx, const uint8_t* in, uint64_t n, uint8_t* out, uint32_t flags);
@@ -1170,6 +1229,49 @@ size_t qfec_wire_parse_revived(const uint8_t* buf, size_t len, size_t packet_num
 size_t qfec_wire_fec_packet_body(uint64_t packet_number, uint64_t fec_group, int entropy_flag,
                                  const uint8_t* redundancy, size_t redundancy_len, uint8_t* buf,
                                  size_t cap);
+/* The v<=31 ack frame, the host mirror of qfec_write_ack_frames
+ * (AppendAckFrameAndTypeByte with GetAckFrameInfo, and ProcessAckFrame,
+ * quic_framer.cc:1400-1495).  The write takes the largest observed and its
+ * entropy hash, the missing packets as n_ranges half-open intervals [range_lo[i],
+ * range_hi[i]), ascending, the revived numbers, ascending, the ack delay in
+ * microseconds (UINT64_MAX: infinite) and whether the ack was cut already, and
+ * writes the frame into buf[0..cap), cap being the room at the frame's first
+ * byte:
+ *   every interval is split into nack ranges of at most 256 numbers; max_delta
+ *     is the largest gap between two intervals or from the last missing number
+ *     to the largest observed, taken before any truncation; ll and mm are the
+ *     minimal lengths (1, 2, 4, 6) of the largest observed and of max_delta;
+ *   max_num_ranges = min(255, (cap - 1 - (4 + ll) - 1) / (mm + 1)); with more
+ *     ranges the lowest max_num_ranges are kept, the largest observed written is
+ *     (start of the first one dropped) - 1, the hash is entropy_up_to(user, that
+ *     number) and the truncated bit is set; ll stays;
+ *   type 0x40 | nacks << 5 | truncated << 4 | flags(ll) << 2 | flags(mm), hash,
+ *     largest (ll bytes, little-endian), the delay as ufloat16, a timestamp
+ *     count of 0 unless truncated; with no range the frame ends there; else the
+ *     range count, the ranges from the highest down as (missing_delta in mm
+ *     bytes, length - 1), the revived count and, ll bytes each, the newest
+ *     revived numbers at or below the largest written, newest first, at most
+ *     min(255, (room - 1) / ll).
+ * wire_largest, wire_hash and wire_truncated (each may be NULL) receive what the
+ * frame says.  Returns the frame's length; 0, with nothing stored, where the
+ * reference writer fails for want of room for a mandatory byte.  The parse is
+ * the inverse: the ranges merged back into maximal intervals (the CSR form of
+ * qfec_entropy_validate_batch; range_lo, range_hi and revived have room for 255
+ * entries), the delay as the ufloat16 written, a timestamp block skipped over.
+ * Returns the bytes consumed, or 0 and the framer's error string in
+ * qfec_last_error(NULL). */
+typedef uint8_t (*qfec_entropy_up_to_fn)(void* user, uint64_t packet_number);
+size_t qfec_wire_write_ack_frame(uint64_t largest_observed, uint8_t entropy_hash,
+                                 const uint64_t* range_lo, const uint64_t* range_hi,
+                                 size_t n_ranges, const uint64_t* revived, size_t n_revived,
+                                 uint64_t ack_delay_us, int truncated,
+                                 qfec_entropy_up_to_fn entropy_up_to, void* user, uint8_t* buf,
+                                 size_t cap, uint64_t* wire_largest, uint8_t* wire_hash,
+                                 int* wire_truncated);
+size_t qfec_wire_parse_ack_frame(const uint8_t* buf, size_t len, uint64_t* largest_observed,
+                                 uint8_t* entropy_hash, uint16_t* delay_ufloat16, int* truncated,
+                                 uint64_t* range_lo, uint64_t* range_hi, size_t* n_ranges,
+                                 uint64_t* revived, size_t* n_revived);
 
 /* ---- packet protection around FEC (ENCRYPTION_NONE) -------------------- */
 /* The NULL packet protection libquic applies before the handshake completes:

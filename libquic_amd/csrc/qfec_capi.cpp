@@ -1159,6 +1159,61 @@ size_t qfec_wire_fec_packet_body(uint64_t packet_number, uint64_t fec_group, int
   return n;
 }
 
+size_t qfec_wire_write_ack_frame(uint64_t largest_observed, uint8_t entropy_hash,
+                                 const uint64_t* range_lo, const uint64_t* range_hi,
+                                 size_t n_ranges, const uint64_t* revived, size_t n_revived,
+                                 uint64_t ack_delay_us, int truncated,
+                                 qfec_entropy_up_to_fn entropy_up_to, void* user, uint8_t* buf,
+                                 size_t cap, uint64_t* wire_largest, uint8_t* wire_hash,
+                                 int* wire_truncated) {
+  if (((!range_lo || !range_hi) && n_ranges) || (!revived && n_revived) || (!buf && cap))
+    return fail(nullptr, 0, "null buffer"), 0;
+  net::AckFrameFields f, w;
+  f.largest_observed = largest_observed;
+  f.entropy_hash = entropy_hash;
+  for (size_t i = 0; i < n_ranges; ++i) f.missing.emplace_back(range_lo[i], range_hi[i]);
+  f.revived.assign(revived, revived + n_revived);
+  f.ack_delay_us = ack_delay_us;
+  f.truncated = truncated != 0;
+  const size_t n = net::WriteAckFrame(f, entropy_up_to, user, buf, cap, &w);
+  if (n == 0) {
+    fail(nullptr, 0, "ack frame: no room for a mandatory byte, or an empty interval");
+    return 0;
+  }
+  if (wire_largest) *wire_largest = w.largest_observed;
+  if (wire_hash) *wire_hash = w.entropy_hash;
+  if (wire_truncated) *wire_truncated = w.truncated;
+  return n;
+}
+
+size_t qfec_wire_parse_ack_frame(const uint8_t* buf, size_t len, uint64_t* largest_observed,
+                                 uint8_t* entropy_hash, uint16_t* delay_ufloat16, int* truncated,
+                                 uint64_t* range_lo, uint64_t* range_hi, size_t* n_ranges,
+                                 uint64_t* revived, size_t* n_revived) {
+  if ((!buf && len) || !largest_observed || !entropy_hash || !delay_ufloat16 || !truncated ||
+      !range_lo || !range_hi || !n_ranges || !revived || !n_revived)
+    return fail(nullptr, 0, "null buffer"), 0;
+  net::AckFrameFields f;
+  std::string err;
+  const size_t n = net::ParseAckFrame(buf, len, &f, &err);
+  if (n == 0) {
+    fail(nullptr, 0, "%s", err.c_str());
+    return 0;
+  }
+  *largest_observed = f.largest_observed;
+  *entropy_hash = f.entropy_hash;
+  *delay_ufloat16 = static_cast<uint16_t>(f.ack_delay_us);
+  *truncated = f.truncated;
+  for (size_t i = 0; i < f.missing.size(); ++i) {
+    range_lo[i] = f.missing[i].first;
+    range_hi[i] = f.missing[i].second;
+  }
+  *n_ranges = f.missing.size();
+  std::copy(f.revived.begin(), f.revived.end(), revived);
+  *n_revived = f.revived.size();
+  return n;
+}
+
 qfec_ctx* qfec_create(int device) {
   int count = 0;
   hipError_t e = hipGetDeviceCount(&count);
@@ -2745,6 +2800,64 @@ int qfec_build_acks(qfec_ctx* ctx, const uint32_t* ack_conn, uint64_t n_acks,
   qfec::acks_scratch_layout(a, ctx->d_revive);
   QFEC_HIP(ctx, qfec::launch_build_acks(a, ctx->stream));
   return revive_scratch_release(ctx);
+}
+
+// QuicFramer::AppendAckFrameAndTypeByte (v<=31, with the revived tail) over the
+// acks qfec_build_acks left on the device: one kernel on the stream, no scratch.
+int qfec_write_ack_frames(qfec_ctx* ctx, const uint32_t* ack_conn, uint64_t n_acks,
+                          const uint64_t* largest_observed, const uint8_t* entropy_hash,
+                          const uint8_t* truncated, const uint32_t* range_ptr,
+                          const uint64_t* range_lo, const uint64_t* range_hi,
+                          const uint32_t* rev_ptr, const uint64_t* rev_pn,
+                          const uint64_t* ack_delay_us, const uint8_t* rcv_cells,
+                          uint64_t n_conns, uint32_t window, uint8_t* out,
+                          const uint64_t* out_off, const uint16_t* out_cap, uint32_t prefix_len,
+                          uint16_t* out_len, uint64_t* wire_largest, uint8_t* wire_hash,
+                          uint8_t* ack_status, uint64_t* counts, uint32_t flags) {
+  const char* const what = "write ack frames";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_device_only(ctx, what, flags))) return rc;
+  if (n_acks == 0) return zero_counts(ctx, counts, qfec::kAckWireCounts);
+  if (!ack_conn || !largest_observed || !entropy_hash || !truncated || !range_ptr || !range_lo ||
+      !range_hi || !rev_ptr || !out || !out_off || !out_cap || !out_len || !wire_largest ||
+      !wire_hash || !ack_status || (n_conns != 0 && !rcv_cells))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: null buffer (only ack_delay_us, rev_pn, counts and the ring of no "
+                "connection may be NULL)", what);
+  if ((rc = check_ack_window(ctx, what, window, rcv_cells))) return rc;
+  if (n_conns >= (1ull << 32) || n_acks >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: 2^32 or more connections or acks", what);
+  if (prefix_len > qfec::kAckWireMaxPrefix)
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: prefix_len %u above %u", what, prefix_len,
+                qfec::kAckWireMaxPrefix);
+  qfec::AckWireArgs a{};
+  a.ack_conn = ack_conn;
+  a.n_acks = (uint32_t)n_acks;
+  a.largest_observed = reinterpret_cast<const unsigned long long*>(largest_observed);
+  a.entropy_hash = entropy_hash;
+  a.truncated = truncated;
+  a.range_ptr = range_ptr;
+  a.range_lo = reinterpret_cast<const unsigned long long*>(range_lo);
+  a.range_hi = reinterpret_cast<const unsigned long long*>(range_hi);
+  a.rev_ptr = rev_ptr;
+  a.rev_pn = reinterpret_cast<const unsigned long long*>(rev_pn);
+  a.ack_delay_us = reinterpret_cast<const unsigned long long*>(ack_delay_us);
+  a.rcv_cells = rcv_cells;
+  a.n_conns = (uint32_t)n_conns;
+  a.window = window;
+  a.out = out;
+  a.out_off = reinterpret_cast<const unsigned long long*>(out_off);
+  a.out_cap = out_cap;
+  a.prefix_len = prefix_len;
+  a.out_len = out_len;
+  a.wire_largest = reinterpret_cast<unsigned long long*>(wire_largest);
+  a.wire_hash = wire_hash;
+  a.ack_status = ack_status;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.err = ctx->d_err;
+  a.ncu = ctx->ncu;
+  QFEC_HIP(ctx, qfec::launch_write_ack_frames(a, ctx->stream));
+  return QFEC_OK;
 }
 
 // qfec_revive_accumulated with the group's K and map kept per slot, where

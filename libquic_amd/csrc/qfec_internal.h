@@ -594,6 +594,40 @@ inline void acks_scratch_layout(AcksArgs& a, void* block) {
 // Three launches on s (count, scan, fill), ordered by the stream alone.
 hipError_t launch_build_acks(const AcksArgs& a, hipStream_t s);
 
+// The built acks as v<=31 ack frames (qfec_write_ack_frames): the build's
+// outputs and the ring, read only.
+constexpr uint32_t kAckWireCounts = 4;      // the acks per QFEC_ACKW_* status
+constexpr uint32_t kAckWireMaxPrefix = 64;  // prefix_len: a packet header and private flags
+struct AckWireArgs {
+  const uint32_t* ack_conn;
+  uint32_t n_acks;  // > 0
+  const unsigned long long* largest_observed;
+  const uint8_t* entropy_hash;
+  const uint8_t* truncated;
+  const uint32_t* range_ptr;  // n_acks + 1
+  const unsigned long long* range_lo;
+  const unsigned long long* range_hi;
+  const uint32_t* rev_ptr;              // n_acks + 1
+  const unsigned long long* rev_pn;     // nullable: no ack has a revived number
+  const unsigned long long* ack_delay_us;  // nullable: all infinite
+  const uint8_t* rcv_cells;             // nullable with n_conns == 0
+  uint32_t n_conns;
+  uint32_t window;
+  uint8_t* out;
+  const unsigned long long* out_off;
+  const uint16_t* out_cap;
+  uint32_t prefix_len;  // <= kAckWireMaxPrefix
+  uint16_t* out_len;
+  unsigned long long* wire_largest;
+  uint8_t* wire_hash;
+  uint8_t* ack_status;
+  unsigned long long* counts;  // nullable: kAckWireCounts words
+  uint32_t* err;
+  uint32_t ncu;
+};
+// One memset (counts) and one launch on s.
+hipError_t launch_write_ack_frames(const AckWireArgs& a, hipStream_t s);
+
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch
 // per batch (the launch is most of a small flush's connection-thread cost).

@@ -8,12 +8,15 @@
 //   * Ack-frame revived-packets list (v<=31): count byte + N packet numbers of
 //     the largest-observed length, little-endian (quic_framer.cc:1477-1493
 //     parse, :2307-2317 write; kNumberOfRevivedPacketsSize quic_framer.h:64-65).
+//   * The ack frame itself (v<=31), written and parsed: the host mirror of
+//     qfec_write_ack_frames.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "quic_fec_group.h"
@@ -68,6 +71,45 @@ size_t WriteRevivedPackets(const std::vector<QuicPacketNumber>& revived,
                            size_t packet_number_length, uint8_t* buf, size_t cap);
 size_t ParseRevivedPackets(const uint8_t* buf, size_t len, size_t packet_number_length,
                            std::vector<QuicPacketNumber>* revived, std::string* detailed_error);
+
+// The v<=31 ack frame (QuicFramer::AppendAckFrameAndTypeByte, quic_framer.cc:
+// 2172-2320, GetAckFrameInfo :1005-1033, with the revived tail of
+// integration/libquic_fec.patch; ProcessAckFrame :1400-1495 the other way).
+struct AckFrameFields {
+  QuicPacketNumber largest_observed = 0;
+  uint8_t entropy_hash = 0;
+  // Missing packets, half-open [first, second), ascending and disjoint.
+  std::vector<std::pair<QuicPacketNumber, QuicPacketNumber>> missing;
+  std::vector<QuicPacketNumber> revived;  // ascending
+  uint64_t ack_delay_us = UINT64_MAX;     // UINT64_MAX: infinite (parsed: the ufloat16)
+  bool truncated = false;                 // cut already (the build's max_ranges)
+};
+
+const size_t kMaxAckNackRanges = 255;  // kMaxNackRanges, one count byte
+const uint64_t kAckUFloat16Max = UINT64_C(0x3FFC0000000);  // kUFloat16MaxValue
+
+// QuicDataWriter::WriteUFloat16 (quic_data_writer.cc:47-84).
+uint16_t AckUFloat16(uint64_t value);
+// GetMinSequenceNumberLength: 1, 2, 4 or 6 bytes.
+size_t AckNumberLength(QuicPacketNumber n);
+
+// Writes f into buf[0..cap); cap is the room at the frame's first byte.  Every
+// interval is split into nack ranges of at most 256 numbers; with more ranges
+// than fit, the lowest are kept, the largest observed becomes (first one
+// dropped) - 1 and the hash entropy_up_to(that number).  *written (nullable)
+// receives the largest observed, the hash and the truncated bit of the frame.
+// Receipt times are not written: the timestamp count of a frame that is not
+// truncated is 0.  Returns the frame's length, 0 where the reference writer
+// fails (no room for a mandatory byte) -- nothing is stored then.
+typedef uint8_t (*AckEntropyUpTo)(void* user, QuicPacketNumber packet_number);
+size_t WriteAckFrame(const AckFrameFields& f, AckEntropyUpTo entropy_up_to, void* user,
+                     uint8_t* buf, size_t cap, AckFrameFields* written);
+
+// Parses one ack frame at buf[0] (its type byte).  The nack ranges are merged
+// back into maximal half-open intervals, ascending; ack_delay_us receives the
+// ufloat16 as written.  Returns the bytes consumed or 0 and *detailed_error.
+size_t ParseAckFrame(const uint8_t* buf, size_t len, AckFrameFields* out,
+                     std::string* detailed_error);
 
 // Serialise a complete FEC packet body for the send side: private header
 // (FEC | FEC_GROUP, offset = packet_number - fec_group) followed by the

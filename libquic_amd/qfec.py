@@ -55,6 +55,10 @@ QFEC_RCV_RECORDED = 5
 QFEC_CELL_RECEIVED = 1
 QFEC_CELL_ENTROPY = 2
 QFEC_CELL_REVIVED = 4
+QFEC_ACKW_WRITTEN = 0
+QFEC_ACKW_CUT = 1
+QFEC_ACKW_NO_ROOM = 2
+QFEC_ACKW_RANGE = 3
 MAX_PACKET_SIZE = 1452
 DEFAULT_MAX_PACKET_SIZE = 1350
 MAX_GROUP_PACKETS = 255
@@ -137,6 +141,9 @@ SIGNATURES = [
     ("qfec_build_acks", C.c_int,
      [_vp, _vp, C.c_uint64, _u8p, _vp, _vp, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
       _vp, _u8p, _u8p, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
+    ("qfec_write_ack_frames", C.c_int,
+     [_vp, _vp, C.c_uint64, _vp, _u8p, _u8p, _vp, _vp, _vp, _vp, _vp, _vp, _u8p, C.c_uint64,
+      C.c_uint32, _u8p, _vp, _vp, C.c_uint32, _vp, _vp, _u8p, _u8p, _vp, C.c_uint32]),
     ("qfec_xor_into", C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint32]),
     ("qfec_wire_write_private_header", C.c_size_t, [_vp, _u8p, C.c_size_t]),
     ("qfec_wire_parse_private_header", C.c_size_t,
@@ -145,6 +152,11 @@ SIGNATURES = [
     ("qfec_wire_parse_revived", C.c_size_t, [_u8p, C.c_size_t, C.c_size_t, _vp, _vp]),
     ("qfec_wire_fec_packet_body", C.c_size_t,
      [C.c_uint64, C.c_uint64, C.c_int, _u8p, C.c_size_t, _u8p, C.c_size_t]),
+    ("qfec_wire_write_ack_frame", C.c_size_t,
+     [C.c_uint64, C.c_uint8, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_int, _vp, _vp,
+      _u8p, C.c_size_t, _vp, _vp, _vp]),
+    ("qfec_wire_parse_ack_frame", C.c_size_t,
+     [_u8p, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("qfec_null_encrypt_batch", C.c_int,
      [_vp, _u8p, _vp, _vp, _vp, _vp, C.c_uint64, _u8p, _vp, C.c_uint32]),
     ("qfec_null_decrypt_batch", C.c_int,
@@ -765,6 +777,28 @@ class Context:
             _ptr(rev_ptr), _ptr(rev_pn), flags)
         return self._check(rc)
 
+    def write_ack_frames(self, ack_conn, n_acks, largest_observed, entropy_hash, truncated,
+                         range_ptr, range_lo, range_hi, rev_ptr, rev_pn, rcv_cells, n_conns,
+                         window, out, out_off, out_cap, out_len, wire_largest, wire_hash,
+                         ack_status, *, ack_delay_us=None, prefix_len=0, counts=None, flags=0):
+        """qfec_write_ack_frames, behind build_acks: the built acks as v<=31
+        ack frames.  ack_conn and build_acks' eight outputs; ack_delay_us
+        (uint64, optional: all infinite); the ring rcv_cells, only read.  Ack
+        a's frame goes to out + out_off[a] (uint64) and has out_cap[a]
+        (uint16) bytes of room; with more nack ranges than fit the writer cuts
+        the ack as the framer does.  out_len[a] (uint16) = prefix_len + the
+        frame's length, 0 where nothing was written; wire_largest (uint64) and
+        wire_hash (uint8) as written; ack_status (uint8) a QFEC_ACKW_* value;
+        counts (uint64[4], optional): the acks per status.  Device pointers
+        only; queued on the context's stream."""
+        rc = self.lib.qfec_write_ack_frames(
+            self.ctx, _ptr(ack_conn), n_acks, _ptr(largest_observed), _ptr(entropy_hash),
+            _ptr(truncated), _ptr(range_ptr), _ptr(range_lo), _ptr(range_hi), _ptr(rev_ptr),
+            _ptr(rev_pn), _ptr(ack_delay_us), _ptr(rcv_cells), n_conns, window, _ptr(out),
+            _ptr(out_off), _ptr(out_cap), prefix_len, _ptr(out_len), _ptr(wire_largest),
+            _ptr(wire_hash), _ptr(ack_status), _ptr(counts), flags)
+        return self._check(rc)
+
     def xor_into(self, src, n, dst, *, host=False, mapped=False):
         return self._check(self.lib.qfec_xor_into(self.ctx, _ptr(src), n, _ptr(dst),
                                                   _fl(host, mapped)))
@@ -1018,3 +1052,45 @@ def wire_fec_packet_body(packet_number, fec_group, entropy, redundancy: bytes):
     n = load().qfec_wire_fec_packet_body(packet_number, fec_group, int(entropy),
                                          C.addressof(red), len(redundancy), C.addressof(buf), cap)
     return bytes(buf[:n])
+
+
+ENTROPY_UP_TO = C.CFUNCTYPE(C.c_uint8, C.c_void_p, C.c_uint64)
+
+
+def wire_write_ack_frame(largest, entropy_hash, ranges, revived, delay_us, cap, *, truncated=False,
+                         entropy_up_to=None):
+    """(frame bytes, largest written, hash written, truncated bit) of
+    qfec_wire_write_ack_frame; the bytes are b"" where nothing fits.  ranges:
+    ascending half-open (lo, hi) pairs; delay_us None: infinite; entropy_up_to:
+    a function of a packet number, asked only when the writer cuts."""
+    lo = (C.c_uint64 * max(1, len(ranges)))(*[r[0] for r in ranges])
+    hi = (C.c_uint64 * max(1, len(ranges)))(*[r[1] for r in ranges])
+    rev = (C.c_uint64 * max(1, len(revived)))(*revived)
+    buf = (C.c_uint8 * max(1, cap))()
+    wl, wh, wt = C.c_uint64(0), C.c_uint8(0), C.c_int(0)
+    cb = ENTROPY_UP_TO((lambda user, pn: entropy_up_to(pn) & 0xFF) if entropy_up_to
+                       else (lambda user, pn: 0))
+    n = load().qfec_wire_write_ack_frame(
+        largest, entropy_hash, C.addressof(lo), C.addressof(hi), len(ranges), C.addressof(rev),
+        len(revived), (1 << 64) - 1 if delay_us is None else delay_us, int(truncated),
+        C.cast(cb, C.c_void_p), None, C.addressof(buf), cap, C.addressof(wl), C.addressof(wh),
+        C.addressof(wt))
+    return bytes(buf[:n]), wl.value, wh.value, bool(wt.value)
+
+
+def wire_parse_ack_frame(data: bytes):
+    """(consumed, dict(largest, hash, delay (the ufloat16), truncated, ranges,
+    revived)) or (0, detailed_error)."""
+    buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
+    largest, h, delay, trunc = C.c_uint64(0), C.c_uint8(0), C.c_uint16(0), C.c_int(0)
+    lo, hi, rev = (C.c_uint64 * 255)(), (C.c_uint64 * 255)(), (C.c_uint64 * 255)()
+    n_r, n_v = C.c_size_t(0), C.c_size_t(0)
+    n = load().qfec_wire_parse_ack_frame(
+        C.addressof(buf), len(data), C.addressof(largest), C.addressof(h), C.addressof(delay),
+        C.addressof(trunc), C.addressof(lo), C.addressof(hi), C.addressof(n_r), C.addressof(rev),
+        C.addressof(n_v))
+    if not n:
+        return 0, _last_error()
+    return n, dict(largest=largest.value, hash=h.value, delay=delay.value,
+                   truncated=bool(trunc.value),
+                   ranges=list(zip(lo[:n_r.value], hi[:n_r.value])), revived=list(rev[:n_v.value]))
