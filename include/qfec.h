@@ -48,6 +48,11 @@
  *       offset byte are encrypted) and its writer, for a whole turn: the
  *       opened packets' first bytes become the keys, positions and body
  *       tables the calls above read.
+ *   qfec_scan_frames
+ *       is QuicFramer::ProcessFrameData (quic_framer.cc:1168-1342) and
+ *       QuicConnection's STOP_WAITING bookkeeping, for a whole turn behind the
+ *       parse: a table of the turn's frames, and per connection the newest
+ *       STOP_WAITING, which the retire and the record take as their raises.
  *   qfec_record_received / qfec_build_acks
  *       are QuicReceivedPacketManager with its EntropyTracker
  *       (RecordPacketReceived, the patch's RecordPacketRevived,
@@ -795,7 +800,8 @@ int qfec_assign_slots(qfec_ctx* ctx, const uint64_t* pkt_key, const uint8_t* pkt
  * qfec_accumulate_ragged -> qfec_revive_tracked (-> qfec_record_received ->
  * qfec_build_acks -> qfec_write_ack_frames, below) on one stream, with no sync and
  * no host decision in between.  Per packet the host supplies what the header
- * gives, per connection only the STOP_WAITING thresholds of the turn.
+ * gives, per connection only the STOP_WAITING thresholds of the turn -- or not
+ * even those: qfec_scan_frames, below, reads them out of the opened packets.
  *
  * This is the only call that interprets a key.  A key other than QFEC_NO_KEY
  * reads conn = key >> key_shift and number = key & ((1 << key_shift) - 1),
@@ -986,6 +992,126 @@ int qfec_write_private_headers(qfec_ctx* ctx, uint8_t* bytes, const uint64_t* pk
                                const uint8_t* hdr, const uint8_t* fec_offset,
                                uint64_t n_packets, int quic_version, uint64_t* body_off_out,
                                uint64_t* counts, uint32_t flags);
+
+/* Frames on the device: QuicFramer::ProcessFrameData (quic_framer.cc:1168-1342)
+ * for a whole turn, with a visitor that always returns true, and the
+ * STOP_WAITING bookkeeping of QuicConnection (quic_connection.cc:765-792,
+ * :1009-1016).  The frames lie behind the private header, in the encrypted part
+ * of the packet: for a packet opened on the device they exist only in device
+ * memory, as the private flags did.  The call sits behind qfec_parse_opened and
+ * in front of qfec_retire_groups, and its STOP_WAITING result is what the retire
+ * and the record take as their raises: no host decision is left in the turn.
+ * The rule per packet is qfec_wire_scan_frames', below.
+ *
+ * Inputs, n_packets records in arrival order: packet p's frame area is
+ * body_len[p] bytes at bytes + body_off[p] (the parse's body_off_out and
+ * body_len_out), packet_number[p] and pkt_conn[p] as the parse was given them,
+ * pkt_pn_len[p] the packet number's length on the wire (1, 2, 4 or 6, from the
+ * cleartext public header; STOP_WAITING's delta has that length), hdr[p] the
+ * parse's hdr_out (hdr NULL: every packet an accepted data packet).
+ * frm_status[p], checked in this order:
+ *   hdr[p] >= 0x80 or hdr[p] & 4           QFEC_FRM_SKIPPED: not accepted, or an
+ *                                          FEC packet, whose body is redundancy.
+ *                                          No byte of the packet is read.
+ *   pkt_pn_len[p] not 1, 2, 4 or 6         QFEC_FRM_PN_LEN, a caller error: nothing
+ *                                          read, latched (the next qfec_sync
+ *                                          returns -QUIC_INVALID_FEC_DATA)
+ *   pkt_conn[p] >= n_conns                 QFEC_FRM_RANGE: nothing read, latched
+ *   otherwise                              the walk's verdict, QFEC_FRM_OK ..
+ *                                          QFEC_FRM_TOO_MANY
+ * Only a packet with QFEC_FRM_OK lists frames and takes part in the
+ * STOP_WAITING step.  frm_ptr (n_packets + 1 words) receives the true prefix
+ * sums of the frames listed: packet p's are entries [frm_ptr[p], frm_ptr[p +
+ * 1]) of the table, in the order they lie in the packet, and frm_ptr[n_packets]
+ * is the total whether or not it fits.
+ * The table, struct-of-arrays with room for frm_cap entries; per entry e:
+ *   frm_pkt[e]    the packet's index p
+ *   frm_type[e]   the wire value 0..8, QFEC_FRAME_STREAM, QFEC_FRAME_ACK
+ *   frm_flags[e]  stream: bit 0 fin, bit 1 the frame had a data length; ack: the
+ *                 type byte's low six bits (nacks 0x20, truncated 0x10, lengths)
+ *   frm_off[e]    an offset into bytes: the stream data; the ack's type byte;
+ *                 the reason text of a close or goaway; the bytes behind a
+ *                 padding's type byte
+ *   frm_len[e]    the stream data's length; the ack frame's whole length, so
+ *                 that qfec_wire_parse_ack_frame(bytes + frm_off, frm_len, ...)
+ *                 takes it as it lies; the text's length; the padding's, which
+ *                 is the rest of the packet (QuicPaddingFrame(BytesRemaining()))
+ *   frm_id[e]     stream, rst, window update, blocked: the stream id; goaway:
+ *                 the last good stream; path close: the path id
+ *   frm_val[e]    stream: the stream offset; rst, window update: the byte
+ *                 offset; stop waiting: least_unacked = packet number - delta;
+ *                 ack: the largest observed
+ *   frm_code[e]   rst, close, goaway: the error code as read; stop waiting, ack:
+ *                 the entropy hash
+ * and 0 in every field a kind does not name.  Nothing is stored at or beyond
+ * frm_cap; with frm_cap == 0 the eight table pointers may be NULL.
+ * STOP_WAITING state, caller-allocated, all zero = a new connection, per
+ * connection c < n_conns: sw_seen[c] is largest_seen_packet_with_stop_waiting_,
+ * sw_least[c] and sw_hash[c] are last_stop_waiting_frame_; sw_conn[c] = c is
+ * written by every call with n_packets > 0.  A packet holds a STOP_WAITING if
+ * the last such frame in it has least_unacked > 0 (the reference lets a later
+ * frame overwrite and acts only on a least_unacked above 0).  Among the call's
+ * packets of c with QFEC_FRM_OK that hold one and have packet_number[p] >
+ * sw_seen[c], the one with the largest packet number wins, among copies of that
+ * number the earliest in arrival order; its packet number, least_unacked and
+ * hash become sw_seen[c], sw_least[c] and sw_hash[c].  Every other connection
+ * keeps its three.  The outputs are a pure function of the inputs.  The turn
+ * then passes raise_conn = sw_conn, raise_mark = raise_least = sw_least,
+ * raise_hash = sw_hash with n_raise = n_conns to qfec_retire_groups and
+ * qfec_record_received: a threshold fed again changes nothing in either.
+ * counts[0..12] (may be NULL), written, not added to: packets OK; SKIPPED;
+ * rejected by the walk (NO_FRAMES .. BAD_LEAST); TOO_MANY; PN_LEN or RANGE;
+ * frames listed that are stream, ack, stop waiting, any other kind; the total,
+ * frm_ptr[n_packets]; the entries that did not fit in frm_cap; connections
+ * whose frame was replaced; of those, the ones whose new least_unacked is below
+ * the old sw_least (ValidateStopWaitingFrame's first test: policy, the host's).
+ * No byte outside [body_off[p], body_off[p] + body_len[p]) is read, whatever
+ * the alignment, and at most max_frames frames of a packet are walked.
+ * Where this differs from the reference: a packet whose walk fails lists no
+ * frame (the framer has delivered the ones before the error) and closing the
+ * connection stays with the host, which has frm_status; BAD_LEAST is a verdict
+ * where the reference trips a DCHECK; TOO_MANY is a result, not an error, and
+ * the walk stops at the type byte of frame max_frames + 1 without judging it;
+ * error codes come out raw (the host clamps them to QUIC_LAST_ERROR and
+ * QUIC_STREAM_LAST_ERROR); the reference applies every newer STOP_WAITING in
+ * arrival order, the turn applies the newest one.
+ * Refused on the host (nothing launched, nothing written), in this order:
+ * QFEC_PTR_HOST, QFEC_PTR_MAPPED or QFEC_ASYNC; a NULL buffer other than hdr
+ * and counts, the tables with frm_cap == 0 and the state with n_conns == 0;
+ * quic_version outside 1..33; max_frames outside 1..255; n_packets, n_conns,
+ * frm_cap or n_packets * max_frames >= 2^32 (QFEC_ERR_INTERNAL).  n_packets == 0
+ * succeeds before the buffers are looked at (counts, if given, receives
+ * thirteen zeroes, frm_ptr[0], if given, one).  Device pointers only; the call
+ * only queues work on the context's stream (four kernels in the revive calls'
+ * scratch), never waits and never reads anything back. */
+#define QFEC_FRM_OK 0u
+#define QFEC_FRM_SKIPPED 1u        /* not accepted by the parse, or an FEC packet */
+#define QFEC_FRM_NO_FRAMES 2u      /* "Packet has no frames." */
+#define QFEC_FRM_ILLEGAL_TYPE 3u   /* "Illegal frame type." */
+#define QFEC_FRM_STREAM 4u         /* QUIC_INVALID_STREAM_DATA */
+#define QFEC_FRM_ACK 5u            /* QUIC_INVALID_ACK_DATA */
+#define QFEC_FRM_RST 6u            /* QUIC_INVALID_RST_STREAM_DATA */
+#define QFEC_FRM_CLOSE 7u          /* QUIC_INVALID_CONNECTION_CLOSE_DATA */
+#define QFEC_FRM_GOAWAY 8u         /* QUIC_INVALID_GOAWAY_DATA */
+#define QFEC_FRM_WINDOW_UPDATE 9u  /* QUIC_INVALID_WINDOW_UPDATE_DATA */
+#define QFEC_FRM_BLOCKED 10u       /* QUIC_INVALID_BLOCKED_DATA */
+#define QFEC_FRM_STOP_WAITING 11u  /* QUIC_INVALID_STOP_WAITING_DATA */
+#define QFEC_FRM_PATH_CLOSE 12u    /* QUIC_INVALID_PATH_CLOSE_DATA */
+#define QFEC_FRM_BAD_LEAST 13u     /* STOP_WAITING delta above the packet number */
+#define QFEC_FRM_TOO_MANY 14u      /* more than max_frames frames */
+#define QFEC_FRM_PN_LEN 15u        /* pkt_pn_len not 1, 2, 4 or 6 (latched) */
+#define QFEC_FRM_RANGE 16u         /* connection out of range (latched) */
+#define QFEC_FRAME_STREAM 0x80u    /* frm_type, beside the wire's 0..8 */
+#define QFEC_FRAME_ACK 0x40u
+int qfec_scan_frames(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* body_off,
+                     const uint16_t* body_len, const uint64_t* packet_number,
+                     const uint32_t* pkt_conn, const uint8_t* pkt_pn_len, const uint8_t* hdr,
+                     uint64_t n_packets, int quic_version, uint32_t max_frames,
+                     uint8_t* frm_status, uint32_t* frm_ptr, uint32_t* frm_pkt, uint8_t* frm_type,
+                     uint8_t* frm_flags, uint64_t* frm_off, uint16_t* frm_len, uint32_t* frm_id,
+                     uint64_t* frm_val, uint32_t* frm_code, uint64_t frm_cap, uint64_t* sw_seen,
+                     uint64_t* sw_least, uint8_t* sw_hash, uint32_t* sw_conn, uint64_t n_conns,
+                     uint64_t* counts, uint32_t flags);
 
 /* Ack state on the device: QuicReceivedPacketManager and its EntropyTracker
  * (quic_received_packet_manager.cc:40-131, :144-193, :222-286) for a whole
@@ -1272,6 +1398,34 @@ size_t qfec_wire_parse_ack_frame(const uint8_t* buf, size_t len, uint64_t* large
                                  uint8_t* entropy_hash, uint16_t* delay_ufloat16, int* truncated,
                                  uint64_t* range_lo, uint64_t* range_hi, size_t* n_ranges,
                                  uint64_t* revived, size_t* n_revived);
+/* One packet's frames, the host mirror of qfec_scan_frames' walk
+ * (QuicFramer::ProcessFrameData with a visitor that always returns true): body
+ * is the len <= 65535 bytes behind the private header, quic_version 1..33,
+ * pn_len 1, 2, 4 or 6.  Frame types as the reference reads them, every
+ * multi-byte value little-endian as QuicDataReader reads it:
+ *   1 f d ooo ss  STREAM: id in ss + 1 bytes, offset in 0 or ooo + 1 bytes, with
+ *                 d a 16-bit data length, without it data to the packet's end
+ *   0 1 n t ll mm ACK (the format of versions up to 33), stepped over: hash,
+ *                 largest in ll bytes, ufloat16 delay; unless t a timestamp
+ *                 count k and, k > 0, 5 + 3 (k - 1) bytes; with n a range count
+ *                 times mm + 1 bytes and, version <= 31, a revived count times
+ *                 ll.  The ranges are bounds-checked, not looked at.
+ *   0 0 1 .....   "Illegal frame type."
+ *   0 PADDING, which ends the packet; 1 RST_STREAM 4 + 8 + 4; 2 CONNECTION_CLOSE
+ *   4 + a string with a 16-bit length; 3 GOAWAY 4 + 4 + a string; 4
+ *   WINDOW_UPDATE 4 + 8; 5 BLOCKED 4; 6 STOP_WAITING hash + pn_len bytes of
+ *   delta; 7 PING; 8 PATH_CLOSE 1; 9..31 illegal.
+ * *status receives the verdict, QFEC_FRM_OK or NO_FRAMES .. TOO_MANY; the
+ * arrays, each with room for max_frames entries, the frames read before the
+ * verdict was reached, *n_walked of them, with frm_off counted from body[0].
+ * Returns the frames the packet lists: *n_walked under QFEC_FRM_OK, else 0.
+ * (size_t)-1 and qfec_last_error(NULL) for a NULL pointer, a length above
+ * 65535, a version, pn_len or max_frames (1..255) out of range. */
+size_t qfec_wire_scan_frames(const uint8_t* body, size_t len, int quic_version,
+                             uint64_t packet_number, size_t pn_len, size_t max_frames,
+                             uint8_t* status, size_t* n_walked, uint8_t* frm_type,
+                             uint8_t* frm_flags, uint32_t* frm_off, uint16_t* frm_len,
+                             uint32_t* frm_id, uint64_t* frm_val, uint32_t* frm_code);
 
 /* ---- packet protection around FEC (ENCRYPTION_NONE) -------------------- */
 /* The NULL packet protection libquic applies before the handshake completes:

@@ -154,7 +154,8 @@ def build_tools(force: bool = False) -> list:
 # whose arena slabs outlive them.)
 SAN_TESTS = [("san", "test_quic_fec_group"), ("san", "test_quic_fec_connection"),
              ("tsan", "test_quic_fec_group"), ("san", "test_layout_guard"),
-             ("san", "test_ack_wire")]  # (the ack frame writer and parser of quic_fec_wire.cc)
+             ("san", "test_ack_wire"),  # (the ack frame writer and parser of quic_fec_wire.cc)
+             ("san", "test_scan_frames")]  # (its frame walk)
 # per-test defines: the layout-guard test plays a caller built against a
 # different quic_fec_group.h
 SAN_DEFINES = {"test_layout_guard": ["-DQFEC_TEST_STALE_LAYOUT"]}

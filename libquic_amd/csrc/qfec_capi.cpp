@@ -1214,6 +1214,39 @@ size_t qfec_wire_parse_ack_frame(const uint8_t* buf, size_t len, uint64_t* large
   return n;
 }
 
+size_t qfec_wire_scan_frames(const uint8_t* body, size_t len, int quic_version,
+                             uint64_t packet_number, size_t pn_len, size_t max_frames,
+                             uint8_t* status, size_t* n_walked, uint8_t* frm_type,
+                             uint8_t* frm_flags, uint32_t* frm_off, uint16_t* frm_len,
+                             uint32_t* frm_id, uint64_t* frm_val, uint32_t* frm_code) {
+  const size_t refused = static_cast<size_t>(-1);
+  if ((!body && len) || !status || !n_walked || !frm_type || !frm_flags || !frm_off || !frm_len ||
+      !frm_id || !frm_val || !frm_code)
+    return fail(nullptr, 0, "null buffer"), refused;
+  if (len > 65535 || quic_version < 1 || quic_version > 33 ||
+      (pn_len != 1 && pn_len != 2 && pn_len != 4 && pn_len != 6) || max_frames < 1 ||
+      max_frames > 255)
+    return fail(nullptr, 0,
+                "scan frames: a body above 65535 bytes, quic_version outside [1, 33], pn_len not "
+                "1, 2, 4 or 6, or max_frames outside [1, 255]"),
+           refused;
+  std::vector<net::ScannedFrame> walked;
+  const net::FrameScanStatus s =
+      net::ScanFrames(body, len, quic_version, packet_number, pn_len, max_frames, &walked);
+  for (size_t k = 0; k < walked.size(); ++k) {
+    frm_type[k] = walked[k].type;
+    frm_flags[k] = walked[k].flags;
+    frm_off[k] = walked[k].off;
+    frm_len[k] = walked[k].len;
+    frm_id[k] = walked[k].id;
+    frm_val[k] = walked[k].val;
+    frm_code[k] = walked[k].code;
+  }
+  *status = s;
+  *n_walked = walked.size();
+  return s == net::kFrmOk ? walked.size() : 0;
+}
+
 qfec_ctx* qfec_create(int device) {
   int count = 0;
   hipError_t e = hipGetDeviceCount(&count);
@@ -2653,6 +2686,79 @@ int qfec_write_private_headers(qfec_ctx* ctx, uint8_t* bytes, const uint64_t* pk
   a.ncu = ctx->ncu;
   QFEC_HIP(ctx, qfec::launch_write_private_headers(a, ctx->stream));
   return QFEC_OK;
+}
+
+// QuicFramer::ProcessFrameData over the turn's packets, behind the parse: the
+// frame table, and per connection the newest STOP_WAITING, which the retire and
+// the record take as their raises.  Four kernels on the stream, in the revive
+// calls' scratch.
+int qfec_scan_frames(qfec_ctx* ctx, const uint8_t* bytes, const uint64_t* body_off,
+                     const uint16_t* body_len, const uint64_t* packet_number,
+                     const uint32_t* pkt_conn, const uint8_t* pkt_pn_len, const uint8_t* hdr,
+                     uint64_t n_packets, int quic_version, uint32_t max_frames,
+                     uint8_t* frm_status, uint32_t* frm_ptr, uint32_t* frm_pkt, uint8_t* frm_type,
+                     uint8_t* frm_flags, uint64_t* frm_off, uint16_t* frm_len, uint32_t* frm_id,
+                     uint64_t* frm_val, uint32_t* frm_code, uint64_t frm_cap, uint64_t* sw_seen,
+                     uint64_t* sw_least, uint8_t* sw_hash, uint32_t* sw_conn, uint64_t n_conns,
+                     uint64_t* counts, uint32_t flags) {
+  const char* const what = "scan frames";
+  int rc = begin_queued(ctx, what);
+  if (rc || (rc = check_device_only(ctx, what, flags))) return rc;
+  if (n_packets == 0) {  // an empty table, where it is given
+    if (frm_ptr) QFEC_HIP(ctx, hipMemsetAsync(frm_ptr, 0, sizeof(uint32_t), ctx->stream));
+    return zero_counts(ctx, counts, qfec::kFramesCounts);
+  }
+  if (!bytes || !body_off || !body_len || !packet_number || !pkt_conn || !pkt_pn_len ||
+      !frm_status || !frm_ptr ||
+      (frm_cap != 0 && (!frm_pkt || !frm_type || !frm_flags || !frm_off || !frm_len || !frm_id ||
+                        !frm_val || !frm_code)) ||
+      (n_conns != 0 && (!sw_seen || !sw_least || !sw_hash || !sw_conn)))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: null buffer (only hdr, counts, the tables with frm_cap == 0 and the state "
+                "of no connection may be NULL)", what);
+  if ((rc = check_quic_version(ctx, what, quic_version))) return rc;
+  if (max_frames < 1 || max_frames > 255)
+    return fail(ctx, QFEC_ERR_INTERNAL, "%s: max_frames %u outside [1, 255]", what, max_frames);
+  if (n_packets >= (1ull << 32) || n_conns >= (1ull << 32) || frm_cap >= (1ull << 32) ||
+      n_packets * max_frames >= (1ull << 32))
+    return fail(ctx, QFEC_ERR_INTERNAL,
+                "%s: 2^32 or more packets, connections or table entries (frm_ptr is 32 bits)",
+                what);
+  if ((rc = revive_scratch_acquire_bytes(ctx, qfec::frames_scratch_bytes(n_packets, n_conns))))
+    return rc;
+  qfec::FramesArgs a{};
+  a.bytes = bytes;
+  a.body_off = body_off;
+  a.body_len = body_len;
+  a.packet_number = reinterpret_cast<const unsigned long long*>(packet_number);
+  a.pkt_conn = pkt_conn;
+  a.pkt_pn_len = pkt_pn_len;
+  a.hdr = hdr;
+  a.n_packets = n_packets;
+  a.revived_tail = quic_version <= 31 ? 1u : 0u;
+  a.max_frames = max_frames;
+  a.frm_status = frm_status;
+  a.frm_ptr = frm_ptr;
+  a.frm_pkt = frm_pkt;
+  a.frm_type = frm_type;
+  a.frm_flags = frm_flags;
+  a.frm_off = frm_off;
+  a.frm_len = frm_len;
+  a.frm_id = frm_id;
+  a.frm_val = reinterpret_cast<unsigned long long*>(frm_val);
+  a.frm_code = frm_code;
+  a.frm_cap = (uint32_t)frm_cap;
+  a.sw_seen = reinterpret_cast<unsigned long long*>(sw_seen);
+  a.sw_least = reinterpret_cast<unsigned long long*>(sw_least);
+  a.sw_hash = sw_hash;
+  a.sw_conn = sw_conn;
+  a.n_conns = (uint32_t)n_conns;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.err = ctx->d_err;
+  a.ncu = ctx->ncu;
+  qfec::frames_scratch_layout(a, ctx->d_revive);
+  QFEC_HIP(ctx, qfec::launch_scan_frames(a, ctx->stream));
+  return revive_scratch_release(ctx);
 }
 
 namespace {

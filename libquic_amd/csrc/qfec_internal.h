@@ -628,6 +628,70 @@ struct AckWireArgs {
 // One memset (counts) and one launch on s.
 hipError_t launch_write_ack_frames(const AckWireArgs& a, hipStream_t s);
 
+// qfec_scan_frames: QuicFramer::ProcessFrameData over the turn's packets, behind
+// the parse, and the STOP_WAITING state per connection (rule as include/qfec.h).
+// Scratch, a block of frames_scratch_bytes(n_packets, n_conns): per packet the
+// frames it lists and its last STOP_WAITING, per connection the largest packet
+// number that holds a newer one and the earliest packet with that number.
+constexpr uint32_t kFrmOk = 0, kFrmSkipped = 1, kFrmNoFrames = 2, kFrmIllegalType = 3,
+                   kFrmStream = 4, kFrmAck = 5, kFrmRst = 6, kFrmClose = 7, kFrmGoaway = 8,
+                   kFrmWindowUpdate = 9, kFrmBlocked = 10, kFrmStopWaiting = 11,
+                   kFrmPathClose = 12, kFrmBadLeast = 13, kFrmTooMany = 14, kFrmPnLen = 15,
+                   kFrmRange = 16;
+constexpr uint32_t kFrameStream = 0x80, kFrameAck = 0x40, kFrameStopWaiting = 6;
+constexpr uint32_t kFramesCounts = 13;  // (order as include/qfec.h)
+struct FramesArgs {
+  const uint8_t* bytes;
+  const uint64_t* body_off;
+  const uint16_t* body_len;
+  const unsigned long long* packet_number;
+  const uint32_t* pkt_conn;
+  const uint8_t* pkt_pn_len;
+  const uint8_t* hdr;   // nullable: all accepted data packets
+  uint64_t n_packets;   // 0 < n_packets < 2^32, n_packets * max_frames < 2^32
+  uint32_t revived_tail;  // the ack has its revived tail: quic_version <= 31
+  uint32_t max_frames;    // 1..255
+  uint8_t* frm_status;
+  uint32_t* frm_ptr;  // n_packets + 1
+  uint32_t* frm_pkt;  // the table: all nullable with frm_cap == 0
+  uint8_t* frm_type;
+  uint8_t* frm_flags;
+  uint64_t* frm_off;
+  uint16_t* frm_len;
+  uint32_t* frm_id;
+  unsigned long long* frm_val;
+  uint32_t* frm_code;
+  uint32_t frm_cap;
+  unsigned long long* sw_seen;  // the state: nullable with n_conns == 0
+  unsigned long long* sw_least;
+  uint8_t* sw_hash;
+  uint32_t* sw_conn;
+  uint32_t n_conns;
+  unsigned long long* counts;    // nullable: kFramesCounts words
+  unsigned long long* top;       // scratch: n_conns, zeroed
+  unsigned long long* pkt_least; // scratch: n_packets (written where a packet holds one)
+  uint32_t* pick;                // scratch: n_conns, all ones
+  uint32_t* n_frm;               // scratch: n_packets
+  uint32_t* tile_off;            // scratch: the frames of every kReviveTile packets, then scanned
+  uint8_t* pkt_hash;             // scratch: n_packets
+  uint32_t* err;
+  uint32_t ncu;
+};
+inline uint64_t frames_scratch_bytes(uint64_t n_packets, uint64_t n_conns) {
+  return n_conns * 12 + n_packets * 13 + revive_tiles(n_packets) * 4 + 8;
+}
+inline void frames_scratch_layout(FramesArgs& a, void* block) {
+  a.top = static_cast<unsigned long long*>(block);
+  a.pkt_least = a.top + a.n_conns;
+  a.pick = reinterpret_cast<uint32_t*>(a.pkt_least + a.n_packets);
+  a.n_frm = a.pick + a.n_conns;
+  a.tile_off = a.n_frm + a.n_packets;
+  a.pkt_hash = reinterpret_cast<uint8_t*>(a.tile_off + revive_tiles(a.n_packets));
+}
+// Up to three memsets and four launches on s (count and maximum, scan, fill and
+// pick, set), ordered by the stream alone.  n_packets > 0.
+hipError_t launch_scan_frames(const FramesArgs& a, hipStream_t s);
+
 // Small-batch service (round 4): one resident workgroup that takes mapped
 // ragged batches from a ring in host-mapped memory instead of a kernel launch
 // per batch (the launch is most of a small flush's connection-thread cost).

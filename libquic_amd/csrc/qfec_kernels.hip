@@ -2704,6 +2704,366 @@ __global__ __launch_bounds__(kReviveTile) void ack_write_kernel(AckWireArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Frames on the device (qfec_scan_frames): QuicFramer::ProcessFrameData over a
+// turn's packets, behind the parse, and the newest STOP_WAITING per connection.
+// ---------------------------------------------------------------------------
+// One lane per packet walks its packet's frames, twice:
+//   count : the verdict, the frames the packet lists (n_frm), its last
+//           STOP_WAITING (pkt_least, pkt_hash) and, where that one is newer
+//           than the connection's, a 64-bit atomicMax of the packet number into
+//           the connection's word of the scratch;
+//           nine tallies, and the frames of the trip's 256 packets, a tile;
+//   scan  : one workgroup over the tiles' sums; the total and the overflow;
+//   fill  : frm_ptr[p] from the tile's offset and a workgroup scan of n_frm,
+//           then the walk again over the OK packets, every frame stored at
+//           frm_ptr[p] + its rank where that lies below frm_cap; a packet whose
+//           number is its connection's maximum offers its arrival index to a
+//           32-bit atomicMin;
+//   set   : one lane per connection takes the picked packet's frame.
+// A maximum and a minimum do not depend on the order of their operands, so the
+// atomics show nowhere.  The lanes of a wave follow packets of their own: the
+// walk's loop diverges and holds no shuffle, ballot or barrier; the tallies are
+// taken behind it, where the wave is whole again.  A byte is loaded only under
+// the bounds check that puts it inside [body_off, body_off + body_len), always
+// as a byte, so no alignment matters; a trip consumes at least the type byte
+// and the loop ends at max_frames, so a walk is at most min(max_frames,
+// body_len) trips.  Values are assembled from bytes in 32-bit halves with
+// constant shifts (the gfx950 64-bit shift hazard).
+
+// n <= 8 bytes at p, little-endian; the caller has checked that they lie inside
+__device__ __forceinline__ void frm_get(const uint8_t* p, uint32_t n, uint32_t& lo, uint32_t& hi) {
+  lo = 0u;
+  hi = 0u;
+#pragma unroll
+  for (uint32_t b = 0; b < 4u; ++b)
+    if (b < n) lo |= (uint32_t)p[b] << (8u * b);
+#pragma unroll
+  for (uint32_t b = 4; b < 8u; ++b)
+    if (b < n) hi |= (uint32_t)p[b] << (8u * (b - 4u));
+}
+
+// ReadSequenceNumberLength: 1, 2, 4, 6
+__device__ __forceinline__ uint32_t frm_length(uint32_t c) { return c == 3u ? 6u : 1u << c; }
+
+struct FrmWalk {
+  uint32_t status;  // the verdict
+  uint32_t n;       // frames walked before it
+  uint32_t n_stream, n_ack, n_sw;  // of those
+  bool has_sw;                  // a STOP_WAITING among them whose last has least_unacked > 0
+  unsigned long long sw_least;  // the last one's
+  uint32_t sw_hash;
+};
+
+// Packet p's frames: len > 0 bytes at body, packet number pn in pn_len bytes on
+// the wire.  FILL: frame k goes to entry base + k of the table.
+template <bool FILL>
+__device__ __forceinline__ FrmWalk frames_walk(const FramesArgs& a, const uint8_t* body,
+                                               uint64_t off, uint32_t len, unsigned long long pn,
+                                               uint32_t pn_len, uint32_t p, uint32_t base) {
+  FrmWalk w{kFrmOk, 0u, 0u, 0u, 0u, false, 0ull, 0u};
+  uint32_t o = 0;
+  while (o < len) {
+    if (w.n == a.max_frames) {
+      w.status = kFrmTooMany;
+      break;
+    }
+    const uint32_t at = o, t = body[o];
+    o += 1u;
+    const uint32_t room = len - o;
+    uint32_t type = t, flags = 0, f_off = 0, f_len = 0, id = 0, v_lo = 0, v_hi = 0, code = 0;
+    uint32_t bad = 0, x;
+    bool placed = false;  // the kind names an offset
+    if ((t & 0x80u) != 0u) {  // ProcessStreamFrame: 1 fin len ooo ss
+      const uint32_t idl = (t & 3u) + 1u, ob = (t >> 2) & 7u, ofl = ob != 0u ? ob + 1u : 0u;
+      const bool has_len = (t & 0x20u) != 0u;
+      const uint32_t head = idl + ofl + (has_len ? 2u : 0u);
+      if (room < head) {
+        bad = kFrmStream;
+      } else {
+        frm_get(body + o, idl, id, x);
+        frm_get(body + o + idl, ofl, v_lo, v_hi);
+        uint32_t n = room - head;
+        if (has_len) {
+          uint32_t l;
+          frm_get(body + o + idl + ofl, 2u, l, x);
+          if (l > n) bad = kFrmStream;
+          n = l;
+        }
+        type = kFrameStream;
+        flags = ((t >> 6) & 1u) | (has_len ? 2u : 0u);
+        placed = true;
+        f_off = o + head;
+        f_len = n;
+        o = f_off + n;
+      }
+    } else if ((t & 0x40u) != 0u) {  // ProcessAckFrame, stepped over
+      const uint32_t mm = frm_length(t & 3u), ll = frm_length((t >> 2) & 3u);
+      uint32_t q = o;
+      bool whole = room >= 3u + ll;  // hash, largest, delay
+      if (whole) {
+        code = body[q];
+        frm_get(body + q + 1u, ll, v_lo, v_hi);
+        q += 3u + ll;
+        if ((t & 0x10u) == 0u) {  // ProcessTimestampsInAckFrame
+          whole = q < len;
+          if (whole) {
+            const uint32_t n = body[q];
+            const uint32_t need = n != 0u ? 5u + (n - 1u) * 3u : 0u;
+            q += 1u;
+            whole = len - q >= need;
+            q += need;
+          }
+        }
+        if (whole && (t & 0x20u) != 0u) {
+          whole = q < len;
+          if (whole) {
+            const uint32_t need = (uint32_t)body[q] * (mm + 1u);
+            q += 1u;
+            whole = len - q >= need;
+            q += need;
+          }
+          if (whole && a.revived_tail != 0u) {
+            whole = q < len;
+            if (whole) {
+              const uint32_t need = (uint32_t)body[q] * ll;
+              q += 1u;
+              whole = len - q >= need;
+              q += need;
+            }
+          }
+        }
+      }
+      if (!whole) bad = kFrmAck;
+      type = kFrameAck;
+      flags = t & 0x3Fu;
+      placed = true;
+      f_off = at;
+      f_len = q - at;
+      o = q;
+    } else if ((t & 0x20u) != 0u) {
+      bad = kFrmIllegalType;
+    } else if (t == 0u) {  // PADDING: the rest of the packet
+      placed = true;
+      f_off = o;
+      f_len = room;
+      o = len;
+    } else if (t == 1u) {  // RST_STREAM
+      if (room < 16u) {
+        bad = kFrmRst;
+      } else {
+        frm_get(body + o, 4u, id, x);
+        frm_get(body + o + 4u, 8u, v_lo, v_hi);
+        frm_get(body + o + 12u, 4u, code, x);
+        o += 16u;
+      }
+    } else if (t == 2u || t == 3u) {  // CONNECTION_CLOSE, GOAWAY
+      const uint32_t head = t == 2u ? 6u : 10u, cls = t == 2u ? kFrmClose : kFrmGoaway;
+      if (room < head) {
+        bad = cls;
+      } else {
+        uint32_t n;
+        frm_get(body + o, 4u, code, x);
+        if (t == 3u) frm_get(body + o + 4u, 4u, id, x);
+        frm_get(body + o + head - 2u, 2u, n, x);
+        if (n > room - head) bad = cls;
+        placed = true;
+        f_off = o + head;
+        f_len = n;
+        o = f_off + n;
+      }
+    } else if (t == 4u) {  // WINDOW_UPDATE
+      if (room < 12u) {
+        bad = kFrmWindowUpdate;
+      } else {
+        frm_get(body + o, 4u, id, x);
+        frm_get(body + o + 4u, 8u, v_lo, v_hi);
+        o += 12u;
+      }
+    } else if (t == 5u) {  // BLOCKED
+      if (room < 4u) {
+        bad = kFrmBlocked;
+      } else {
+        frm_get(body + o, 4u, id, x);
+        o += 4u;
+      }
+    } else if (t == kFrameStopWaiting) {  // (the entropy byte: every version up to 33)
+      if (room < 1u + pn_len) {
+        bad = kFrmStopWaiting;
+      } else {
+        uint32_t d_lo, d_hi;
+        code = body[o];
+        frm_get(body + o + 1u, pn_len, d_lo, d_hi);
+        const unsigned long long delta = (unsigned long long)d_hi << 32 | d_lo;
+        if (delta > pn) bad = kFrmBadLeast;
+        const unsigned long long least = pn - delta;
+        v_lo = (uint32_t)least;
+        v_hi = (uint32_t)(least >> 32);
+        o += 1u + pn_len;
+      }
+    } else if (t == 7u) {  // PING
+    } else if (t == 8u) {  // PATH_CLOSE
+      if (room < 1u) {
+        bad = kFrmPathClose;
+      } else {
+        id = body[o];
+        o += 1u;
+      }
+    } else {
+      bad = kFrmIllegalType;
+    }
+    if (bad != 0u) {
+      w.status = bad;
+      break;
+    }
+    const unsigned long long val = (unsigned long long)v_hi << 32 | v_lo;
+    if (FILL) {
+      const uint32_t e = base + w.n;
+      if (e < a.frm_cap) {
+        a.frm_pkt[e] = p;
+        a.frm_type[e] = (uint8_t)type;
+        a.frm_flags[e] = (uint8_t)flags;
+        a.frm_off[e] = placed ? off + f_off : 0ull;
+        a.frm_len[e] = (uint16_t)f_len;
+        a.frm_id[e] = id;
+        a.frm_val[e] = val;
+        a.frm_code[e] = code;
+      }
+    }
+    w.n_stream += (uint32_t)(type == kFrameStream);
+    w.n_ack += (uint32_t)(type == kFrameAck);
+    if (type == kFrameStopWaiting) {
+      w.n_sw += 1u;
+      w.has_sw = val != 0ull;
+      w.sw_least = val;
+      w.sw_hash = code;
+    }
+    w.n += 1u;
+  }
+  return w;
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(kReviveTile) void frames_walk_kernel(FramesArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves * 9];
+  __shared__ uint32_t s_t[kTurnWaves];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  // the wave's packets (uniform): OK, skipped, rejected, too many, caller errors;
+  // and this lane's frames listed: stream, ack, stop waiting, other
+  uint32_t n[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t mine[4] = {0, 0, 0, 0};
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * kReviveTile; p0 < a.n_packets; p0 += step) {
+    const uint64_t p = p0 + tid;
+    const bool in = p < a.n_packets;
+    const uint64_t pc = in ? p : a.n_packets - 1u;  // (clamped, not masked)
+    const uint64_t off = a.body_off[pc];
+    const uint32_t len = a.body_len[pc];
+    const unsigned long long pn = a.packet_number[pc];
+    const uint32_t conn = a.pkt_conn[pc], pn_len = a.pkt_pn_len[pc];
+    if (FILL) {
+      const bool ok = in && a.frm_status[pc] == kFrmOk;  // (OK: conn < n_conns, len > 0)
+      // frm_ptr: the frames of the tiles in front, and of the tile's packets in front
+      uint32_t in_tile;
+      const uint32_t base = a.tile_off[p0 / kReviveTile] +
+                            block_excl_scan<kTurnWaves>(in ? a.n_frm[pc] : 0u, lane, wave, s_t, in_tile);
+      if (in) a.frm_ptr[p] = base;
+      if (ok) {
+        const FrmWalk w =
+            frames_walk<true>(a, a.bytes + off, off, len, pn, pn_len, (uint32_t)p, base);
+        if (w.has_sw && pn == a.top[conn]) atomicMin(&a.pick[conn], (uint32_t)p);
+      }
+    } else {
+      const uint32_t h = a.hdr ? a.hdr[pc] : 0u;
+      uint32_t status;
+      if (h >= kHdrFailed || (h & kPrivateFlagFec) != 0u) status = kFrmSkipped;
+      else if (pn_len != 1u && pn_len != 2u && pn_len != 4u && pn_len != 6u) status = kFrmPnLen;
+      else if (conn >= a.n_conns) status = kFrmRange;
+      else if (len == 0u) status = kFrmNoFrames;
+      else status = kFrmOk;
+      FrmWalk w{status, 0u, 0u, 0u, 0u, false, 0ull, 0u};
+      if (in && status == kFrmOk)
+        w = frames_walk<false>(a, a.bytes + off, off, len, pn, pn_len, (uint32_t)p, 0u);
+      const bool ok = in && w.status == kFrmOk;
+      const uint32_t listed = ok ? w.n : 0u;
+      if (in) {
+        a.frm_status[p] = (uint8_t)w.status;
+        a.n_frm[p] = listed;
+      }
+      // (behind the walk: the wave is whole again)  The trip's packets are one
+      // tile of the scan: its frames, for the one-workgroup pass over the tiles.
+      const uint32_t in_tile = block_sum(wave_sum(listed), lane, wave, s_t);
+      if (tid == 0u) a.tile_off[p0 / kReviveTile] = in_tile;
+      if (ok) {
+        mine[0] += w.n_stream;
+        mine[1] += w.n_ack;
+        mine[2] += w.n_sw;
+        mine[3] += w.n - w.n_stream - w.n_ack - w.n_sw;
+        if (w.has_sw) {
+          a.pkt_least[p] = w.sw_least;
+          a.pkt_hash[p] = (uint8_t)w.sw_hash;
+          if (pn > a.sw_seen[conn]) retire_max(&a.top[conn], pn);
+        }
+      }
+      const uint32_t s = w.status;
+      n[0] += (uint32_t)__popcll(__ballot(ok));
+      n[1] += (uint32_t)__popcll(__ballot(in && s == kFrmSkipped));
+      n[2] += (uint32_t)__popcll(__ballot(in && s >= kFrmNoFrames && s <= kFrmBadLeast));
+      n[3] += (uint32_t)__popcll(__ballot(in && s == kFrmTooMany));
+      n[4] += (uint32_t)__popcll(__ballot(in && (s == kFrmPnLen || s == kFrmRange)));
+    }
+  }
+  if (!FILL) {
+#pragma unroll
+    for (uint32_t c = 0; c < 4u; ++c) n[5u + c] = wave_sum(mine[c]);
+    const uint32_t t = block_sum(n, lane, wave, s_w);
+    if (tid < 9u && t != 0u) {
+      if (a.counts) atomicAdd(&a.counts[tid], (unsigned long long)t);
+      if (tid == 4u) atomicOr(a.err, kErrMissingIndex);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kRvScanBlock) void frames_scan_kernel(FramesArgs a) {
+  __shared__ uint32_t s_w[kRvScanBlock / 64];
+  const uint64_t total =
+      tile_scan_in_place(a.tile_off, (a.n_packets + kReviveTile - 1u) / kReviveTile, s_w);
+  if (threadIdx.x == 0u) {
+    a.frm_ptr[a.n_packets] = (uint32_t)total;
+    if (a.counts) {
+      a.counts[9] = total;
+      a.counts[10] = total > a.frm_cap ? total - a.frm_cap : 0ull;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kReviveTile) void frames_set_kernel(FramesArgs a) {
+  __shared__ uint32_t s_w[kTurnWaves * 2];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t n[2] = {0, 0};  // the wave's connections (uniform): replaced, and with a lower least
+  const uint64_t step = (uint64_t)gridDim.x * kReviveTile;
+  for (uint64_t c0 = (uint64_t)blockIdx.x * kReviveTile; c0 < a.n_conns; c0 += step) {
+    const uint64_t c = c0 + tid;
+    const bool in = c < a.n_conns;
+    const uint32_t cc = (uint32_t)(in ? c : a.n_conns - 1u);  // (clamped, not masked)
+    const uint32_t pick = a.pick[cc];
+    const bool won = in && pick != 0xFFFFFFFFu;  // (a pick is a packet: below n_packets)
+    bool lower = false;
+    if (in) a.sw_conn[cc] = cc;
+    if (won) {
+      const unsigned long long least = a.pkt_least[pick];
+      lower = least < a.sw_least[cc];
+      a.sw_seen[cc] = a.top[cc];
+      a.sw_least[cc] = least;
+      a.sw_hash[cc] = a.pkt_hash[pick];
+    }
+    n[0] += (uint32_t)__popcll(__ballot(won));
+    n[1] += (uint32_t)__popcll(__ballot(lower));
+  }
+  const uint32_t t = block_sum(n, lane, wave, s_w);
+  if (tid < 2u && t != 0u && a.counts) atomicAdd(&a.counts[11u + tid], (unsigned long long)t);
+}
+
 // The recover body over the work list, L >= 16: lanes, windows and loads as
 // fixed_xor_kernel; workgroup step i takes entries [i * gpb, (i + 1) * gpb).
 // `work` and `totals` are separate restrict parameters so that their loads
@@ -5204,6 +5564,23 @@ hipError_t launch_write_ack_frames(const AckWireArgs& a, hipStream_t s) {
       a.counts ? hipMemsetAsync(a.counts, 0, kAckWireCounts * sizeof(uint64_t), s) : hipSuccess;
   const uint32_t wgrid = per_packet_grid((uint64_t)a.n_acks * 64u, a.ncu);  // (a wave per ack)
   return launch_pass(e, ack_write_kernel, wgrid, kReviveTile, s, a);
+}
+
+hipError_t launch_scan_frames(const FramesArgs& a, hipStream_t s) {
+  if (a.n_packets == 0) return hipSuccess;
+  hipError_t e =
+      a.counts ? hipMemsetAsync(a.counts, 0, kFramesCounts * sizeof(uint64_t), s) : hipSuccess;
+  if (e == hipSuccess && a.n_conns != 0)
+    e = hipMemsetAsync(a.top, 0, (size_t)a.n_conns * sizeof(uint64_t), s);
+  if (e == hipSuccess && a.n_conns != 0)
+    e = hipMemsetAsync(a.pick, 0xFF, (size_t)a.n_conns * sizeof(uint32_t), s);
+  const uint32_t pgrid = per_packet_grid(a.n_packets, a.ncu);
+  e = launch_pass(e, frames_walk_kernel<false>, pgrid, kReviveTile, s, a);
+  e = launch_pass(e, frames_scan_kernel, 1, kRvScanBlock, s, a);
+  e = launch_pass(e, frames_walk_kernel<true>, pgrid, kReviveTile, s, a);
+  if (a.n_conns != 0)
+    e = launch_pass(e, frames_set_kernel, per_packet_grid(a.n_conns, a.ncu), kReviveTile, s, a);
+  return e;
 }
 
 hipError_t launch_accumulate_ragged(const AccumulateRaggedArgs& a0, hipStream_t s) {

@@ -296,6 +296,129 @@ size_t ParseAckFrame(const uint8_t* buf, size_t len, AckFrameFields* out,
   return o;
 }
 
+FrameScanStatus ScanFrames(const uint8_t* body, size_t len, int quic_version,
+                           QuicPacketNumber packet_number, size_t packet_number_length,
+                           size_t max_frames, std::vector<ScannedFrame>* walked) {
+  static const size_t kLengths[4] = {1, 2, 4, 6};
+  walked->clear();
+  if (len == 0) return kFrmNoFrames;
+  size_t o = 0;
+  // CanRead(n) of the reader at o
+  const auto can = [&](size_t n) { return len - o >= n; };
+  const auto get = [&](size_t n) {
+    const uint64_t v = GetNumber(body + o, n);
+    o += n;
+    return v;
+  };
+  while (o < len) {
+    if (walked->size() == max_frames) return kFrmTooMany;
+    const size_t at = o;
+    const uint8_t t = body[o++];
+    ScannedFrame f;
+    if (t & 0x80) {  // ProcessStreamFrame: 1 fin len ooo ss
+      const size_t id_len = (t & 3) + 1, off_bits = (t >> 2) & 7;
+      const size_t off_len = off_bits ? off_bits + 1 : 0;
+      const bool has_len = (t & 0x20) != 0;
+      if (!can(id_len + off_len + (has_len ? 2 : 0))) return kFrmStream;
+      f.type = kFrameTypeStream;
+      f.flags = static_cast<uint8_t>(((t & 0x40) ? 1 : 0) | (has_len ? 2 : 0));
+      f.id = static_cast<uint32_t>(get(id_len));
+      f.val = get(off_len);
+      const size_t n = has_len ? static_cast<size_t>(get(2)) : len - o;
+      if (!can(n)) return kFrmStream;
+      f.off = static_cast<uint32_t>(o);
+      f.len = static_cast<uint16_t>(n);
+      o += n;
+    } else if (t & 0x40) {  // ProcessAckFrame, stepped over
+      const size_t mm = kLengths[t & 3], ll = kLengths[(t >> 2) & 3];
+      if (!can(1 + ll + 2)) return kFrmAck;
+      f.type = kFrameTypeAck;
+      f.flags = t & 0x3F;
+      f.code = static_cast<uint32_t>(get(1));
+      f.val = get(ll);
+      o += 2;
+      if (!(t & 0x10)) {  // ProcessTimestampsInAckFrame
+        if (!can(1)) return kFrmAck;
+        const size_t n = static_cast<size_t>(get(1));
+        const size_t bytes = n ? 5 + (n - 1) * 3 : 0;
+        if (!can(bytes)) return kFrmAck;
+        o += bytes;
+      }
+      if (t & 0x20) {
+        if (!can(1)) return kFrmAck;
+        const size_t ranges = static_cast<size_t>(get(1)) * (mm + 1);
+        if (!can(ranges)) return kFrmAck;
+        o += ranges;
+        if (quic_version <= 31) {
+          if (!can(1)) return kFrmAck;
+          const size_t revived = static_cast<size_t>(get(1)) * ll;
+          if (!can(revived)) return kFrmAck;
+          o += revived;
+        }
+      }
+      f.off = static_cast<uint32_t>(at);
+      f.len = static_cast<uint16_t>(o - at);
+    } else if (t & 0x20) {
+      return kFrmIllegalType;
+    } else {
+      f.type = t;
+      switch (t) {
+        case 0:  // PADDING: the rest of the packet
+          f.off = static_cast<uint32_t>(o);
+          f.len = static_cast<uint16_t>(len - o);
+          o = len;
+          break;
+        case 1:  // RST_STREAM
+          if (!can(16)) return kFrmRst;
+          f.id = static_cast<uint32_t>(get(4));
+          f.val = get(8);
+          f.code = static_cast<uint32_t>(get(4));
+          break;
+        case 2:    // CONNECTION_CLOSE
+        case 3: {  // GOAWAY
+          const FrameScanStatus bad = t == 2 ? kFrmClose : kFrmGoaway;
+          if (!can(t == 2 ? 6 : 10)) return bad;
+          f.code = static_cast<uint32_t>(get(4));
+          if (t == 3) f.id = static_cast<uint32_t>(get(4));
+          const size_t n = static_cast<size_t>(get(2));
+          if (!can(n)) return bad;
+          f.off = static_cast<uint32_t>(o);
+          f.len = static_cast<uint16_t>(n);
+          o += n;
+          break;
+        }
+        case 4:  // WINDOW_UPDATE
+          if (!can(12)) return kFrmWindowUpdate;
+          f.id = static_cast<uint32_t>(get(4));
+          f.val = get(8);
+          break;
+        case 5:  // BLOCKED
+          if (!can(4)) return kFrmBlocked;
+          f.id = static_cast<uint32_t>(get(4));
+          break;
+        case 6: {  // STOP_WAITING (the entropy byte: every version up to 33)
+          if (!can(1 + packet_number_length)) return kFrmStopWaiting;
+          f.code = static_cast<uint32_t>(get(1));
+          const uint64_t delta = get(packet_number_length);
+          if (delta > packet_number) return kFrmBadLeast;
+          f.val = packet_number - delta;
+          break;
+        }
+        case 7:  // PING
+          break;
+        case 8:  // PATH_CLOSE
+          if (!can(1)) return kFrmPathClose;
+          f.id = static_cast<uint32_t>(get(1));
+          break;
+        default:
+          return kFrmIllegalType;
+      }
+    }
+    walked->push_back(f);
+  }
+  return kFrmOk;
+}
+
 size_t SerializeFecPacketBody(QuicPacketNumber packet_number, QuicFecGroupNumber fec_group,
                               bool entropy_flag, StringPiece redundancy, uint8_t* buf,
                               size_t cap) {

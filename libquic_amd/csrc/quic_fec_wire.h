@@ -111,6 +111,53 @@ size_t WriteAckFrame(const AckFrameFields& f, AckEntropyUpTo entropy_up_to, void
 size_t ParseAckFrame(const uint8_t* buf, size_t len, AckFrameFields* out,
                      std::string* detailed_error);
 
+// One packet's frames (QuicFramer::ProcessFrameData, quic_framer.cc:1168-1342,
+// with a visitor that always returns true): the host mirror of
+// qfec_scan_frames.  Verdicts, the QFEC_FRM_* of include/qfec.h.
+enum FrameScanStatus : uint8_t {
+  kFrmOk = 0,
+  kFrmSkipped = 1,        // (the device call's: not accepted, or an FEC packet)
+  kFrmNoFrames = 2,       // "Packet has no frames."
+  kFrmIllegalType = 3,    // "Illegal frame type."
+  kFrmStream = 4,         // QUIC_INVALID_STREAM_DATA
+  kFrmAck = 5,            // QUIC_INVALID_ACK_DATA
+  kFrmRst = 6,            // QUIC_INVALID_RST_STREAM_DATA
+  kFrmClose = 7,          // QUIC_INVALID_CONNECTION_CLOSE_DATA
+  kFrmGoaway = 8,         // QUIC_INVALID_GOAWAY_DATA
+  kFrmWindowUpdate = 9,   // QUIC_INVALID_WINDOW_UPDATE_DATA
+  kFrmBlocked = 10,       // QUIC_INVALID_BLOCKED_DATA
+  kFrmStopWaiting = 11,   // QUIC_INVALID_STOP_WAITING_DATA
+  kFrmPathClose = 12,     // QUIC_INVALID_PATH_CLOSE_DATA
+  kFrmBadLeast = 13,      // STOP_WAITING delta above the packet number
+  kFrmTooMany = 14,       // more than max_frames frames
+  kFrmPnLen = 15,         // (the device call's: pkt_pn_len not 1, 2, 4 or 6)
+  kFrmRange = 16,         // (the device call's: connection out of range)
+};
+const uint8_t kFrameTypeStream = 0x80, kFrameTypeAck = 0x40;  // frm_type beside the wire's 0..8
+
+struct ScannedFrame {
+  uint8_t type = 0;   // the wire value 0..8, kFrameTypeStream, kFrameTypeAck
+  uint8_t flags = 0;  // stream: 1 fin, 2 had a length; ack: the type byte's low six bits
+  uint32_t off = 0;   // from the body's first byte: stream data, the ack's type byte, the reason
+                      // text of a close or goaway, the bytes behind a padding's type byte
+  uint16_t len = 0;   // stream data, the whole ack frame, the text, the padding
+  uint32_t id = 0;    // stream id; goaway: last good stream; path close: path id
+  uint64_t val = 0;   // stream offset; rst, window update: byte offset; stop waiting: least
+                      // unacked; ack: largest observed
+  uint32_t code = 0;  // rst, close, goaway: the error code as read; stop waiting, ack: the hash
+};
+
+// Walks body[0..len) (len <= 65535), the bytes behind the private header, for
+// quic_version 1..33 and a packet number length of 1, 2, 4 or 6.  *walked
+// receives the frames read before the verdict was reached, whatever it is (at
+// most max_frames); a packet lists its frames only under kFrmOk.  Multi-byte
+// values are little-endian, as QuicDataReader reads them.  The ack is stepped
+// over: its ranges are bounds-checked, not looked at.  No byte at or beyond len
+// is read.
+FrameScanStatus ScanFrames(const uint8_t* body, size_t len, int quic_version,
+                           QuicPacketNumber packet_number, size_t packet_number_length,
+                           size_t max_frames, std::vector<ScannedFrame>* walked);
+
 // Serialise a complete FEC packet body for the send side: private header
 // (FEC | FEC_GROUP, offset = packet_number - fec_group) followed by the
 // redundancy (QuicFecGroup::PayloadParity()).  Returns bytes written or 0.

@@ -55,6 +55,25 @@ QFEC_RCV_RECORDED = 5
 QFEC_CELL_RECEIVED = 1
 QFEC_CELL_ENTROPY = 2
 QFEC_CELL_REVIVED = 4
+QFEC_FRM_OK = 0
+QFEC_FRM_SKIPPED = 1
+QFEC_FRM_NO_FRAMES = 2
+QFEC_FRM_ILLEGAL_TYPE = 3
+QFEC_FRM_STREAM = 4
+QFEC_FRM_ACK = 5
+QFEC_FRM_RST = 6
+QFEC_FRM_CLOSE = 7
+QFEC_FRM_GOAWAY = 8
+QFEC_FRM_WINDOW_UPDATE = 9
+QFEC_FRM_BLOCKED = 10
+QFEC_FRM_STOP_WAITING = 11
+QFEC_FRM_PATH_CLOSE = 12
+QFEC_FRM_BAD_LEAST = 13
+QFEC_FRM_TOO_MANY = 14
+QFEC_FRM_PN_LEN = 15
+QFEC_FRM_RANGE = 16
+QFEC_FRAME_STREAM = 0x80
+QFEC_FRAME_ACK = 0x40
 QFEC_ACKW_WRITTEN = 0
 QFEC_ACKW_CUT = 1
 QFEC_ACKW_NO_ROOM = 2
@@ -134,6 +153,10 @@ SIGNATURES = [
       _u8p, _u8p, _vp, C.c_uint32]),
     ("qfec_write_private_headers", C.c_int,
      [_vp, _u8p, _vp, _u8p, _u8p, C.c_uint64, C.c_int, _vp, _vp, C.c_uint32]),
+    ("qfec_scan_frames", C.c_int,
+     [_vp, _u8p, _vp, _vp, _vp, _vp, _u8p, _u8p, C.c_uint64, C.c_int, C.c_uint32, _u8p, _vp, _vp,
+      _u8p, _u8p, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _u8p, _vp, C.c_uint64, _vp,
+      C.c_uint32]),
     ("qfec_record_received", C.c_int,
      [_vp, _vp, _vp, _u8p, _u8p, C.c_uint64, _u8p, _u8p, _vp, _vp, C.c_uint64, C.c_uint64,
       C.c_uint32, _vp, _vp, _u8p, C.c_uint64, _u8p, _vp, _vp, _u8p, C.c_uint64, C.c_uint32, _u8p,
@@ -157,6 +180,9 @@ SIGNATURES = [
       _u8p, C.c_size_t, _vp, _vp, _vp]),
     ("qfec_wire_parse_ack_frame", C.c_size_t,
      [_u8p, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("qfec_wire_scan_frames", C.c_size_t,
+     [_u8p, C.c_size_t, C.c_int, C.c_uint64, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp,
+      _vp, _vp, _vp]),
     ("qfec_null_encrypt_batch", C.c_int,
      [_vp, _u8p, _vp, _vp, _vp, _vp, C.c_uint64, _u8p, _vp, C.c_uint32]),
     ("qfec_null_decrypt_batch", C.c_int,
@@ -725,6 +751,38 @@ class Context:
                                                  _ptr(body_off_out), _ptr(counts), flags)
         return self._check(rc)
 
+    def scan_frames(self, data, body_off, body_len, packet_number, pkt_conn, pkt_pn_len,
+                    n_packets, quic_version, max_frames, frm_status, frm_ptr, sw_seen, sw_least,
+                    sw_hash, sw_conn, n_conns, *, hdr=None, frm_pkt=None, frm_type=None,
+                    frm_flags=None, frm_off=None, frm_len=None, frm_id=None, frm_val=None,
+                    frm_code=None, frm_cap=0, counts=None, flags=0):
+        """qfec_scan_frames, behind parse_opened and in front of retire_groups:
+        QuicFramer::ProcessFrameData over the turn's packets.  Packet p's frame
+        area is body_len[p] (uint16) bytes at data + body_off[p] (uint64), the
+        parse's outputs; packet_number (uint64), pkt_conn (uint32) and
+        pkt_pn_len (uint8: 1, 2, 4 or 6) come from the public header, hdr
+        (uint8, optional) from the parse.  frm_status (uint8[n_packets]) is a
+        QFEC_FRM_* verdict; frm_ptr (uint32[n_packets + 1]) the prefix sums of
+        the frames listed, which only an OK packet does.  The table, with room
+        for frm_cap entries: frm_pkt (uint32), frm_type and frm_flags (uint8),
+        frm_off (uint64, into data), frm_len (uint16), frm_id (uint32), frm_val
+        (uint64), frm_code (uint32).  The STOP_WAITING state per connection,
+        all zero when new: sw_seen and sw_least (uint64), sw_hash (uint8);
+        sw_conn (uint32) receives 0 .. n_conns - 1, and the four go to
+        retire_groups and record_received as the raises with n_raise =
+        n_conns.  counts (uint64[13], optional): packets OK, skipped, rejected,
+        too many, caller errors; frames stream, ack, stop waiting, other; the
+        total; the overflow; connections replaced; of those with a lower
+        least_unacked.  Device pointers only; queued on the context's stream."""
+        rc = self.lib.qfec_scan_frames(
+            self.ctx, _ptr(data), _ptr(body_off), _ptr(body_len), _ptr(packet_number),
+            _ptr(pkt_conn), _ptr(pkt_pn_len), _ptr(hdr), n_packets, quic_version, max_frames,
+            _ptr(frm_status), _ptr(frm_ptr), _ptr(frm_pkt), _ptr(frm_type), _ptr(frm_flags),
+            _ptr(frm_off), _ptr(frm_len), _ptr(frm_id), _ptr(frm_val), _ptr(frm_code), frm_cap,
+            _ptr(sw_seen), _ptr(sw_least), _ptr(sw_hash), _ptr(sw_conn), n_conns, _ptr(counts),
+            flags)
+        return self._check(rc)
+
     def record_received(self, rcv_cells, rcv_least, rcv_largest, rcv_hash, n_conns, window, *,
                         packet_number=None, pkt_conn=None, n_packets=0, rcv_out=None, hdr=None,
                         entropy=None, status=None, revived_idx=None, slot=None, slot_key=None,
@@ -1094,3 +1152,26 @@ def wire_parse_ack_frame(data: bytes):
     return n, dict(largest=largest.value, hash=h.value, delay=delay.value,
                    truncated=bool(trunc.value),
                    ranges=list(zip(lo[:n_r.value], hi[:n_r.value])), revived=list(rev[:n_v.value]))
+
+
+def wire_scan_frames(body: bytes, quic_version, packet_number, pn_len, max_frames=255):
+    """(status, listed, walked) of qfec_wire_scan_frames: the QFEC_FRM_* verdict,
+    the frames the packet lists (none unless the verdict is OK) and the frames
+    read before the verdict was reached, each a tuple (type, flags, off, len,
+    id, val, code) with off counted from the body's first byte."""
+    import numpy as np
+    buf = (C.c_uint8 * max(1, len(body))).from_buffer_copy(body or b"\0")
+    m = max(1, max_frames)
+    t, fl = np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+    off, ln = np.zeros(m, np.uint32), np.zeros(m, np.uint16)
+    fid, val, code = np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
+    status, n_walked = C.c_uint8(0), C.c_size_t(0)
+    n = load().qfec_wire_scan_frames(
+        C.addressof(buf), len(body), quic_version, packet_number, pn_len, max_frames,
+        C.addressof(status), C.addressof(n_walked), t.ctypes.data, fl.ctypes.data, off.ctypes.data,
+        ln.ctypes.data, fid.ctypes.data, val.ctypes.data, code.ctypes.data)
+    if n == C.c_size_t(-1).value:
+        raise QfecError(-1, _last_error())
+    walked = [(int(t[k]), int(fl[k]), int(off[k]), int(ln[k]), int(fid[k]), int(val[k]),
+               int(code[k])) for k in range(n_walked.value)]
+    return status.value, walked[:n], walked
