@@ -61,6 +61,35 @@ def random_turn(rng, state, n_packets, n_groups=0, n_raise=0, hdr=True, entropy=
     return t
 
 
+def grown_state(rng, n_conns, window=64, calls=2, per_conn=20):
+    """a state of many connections grown by `calls` random turns through the
+    whole-array rule: missing, revived and raised packets on every side"""
+    state = A.new_state(n_conns, window)
+    for _ in range(calls):
+        turn = random_turn(rng, state, per_conn * n_conns, n_groups=6 * n_conns,
+                           n_raise=n_conns // 3)
+        state = A.record_received_np(state, **turn)["state"]
+    return state
+
+
+def acks_ending_full(rng, state, n_acks, max_ranges, max_revived, truncated=False):
+    """ack_conn of n_acks random connections (repeats included); the last one's
+    ack has intervals and (where any may be listed) revived packets, and is
+    truncated at max_ranges if asked"""
+    n_conns = len(state["least"])
+    every = A.build_acks_np(state, np.arange(n_conns), max_ranges, max_revived)
+    such = np.diff(every["range_ptr"]) > 0
+    if max_revived:
+        such &= np.diff(every["rev_ptr"]) > 0
+    if truncated:
+        such &= every["truncated"] != 0
+    such = np.flatnonzero(such)
+    assert such.size, "no connection has such an ack"
+    conn = rng.integers(0, n_conns, n_acks).astype(np.uint32)
+    conn[-1] = such[rng.integers(0, such.size)]
+    return conn
+
+
 def fixture():
     return np.load(GOLDEN)
 

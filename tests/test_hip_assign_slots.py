@@ -21,6 +21,7 @@ import assign_rule as AS
 import bin_rule as B
 from libquic_amd import qfec
 from test_hip_accumulate_ragged import dview
+from turn_sizes import GRID_PER_CU, grid_wrap, ncu
 
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
@@ -174,6 +175,37 @@ def test_a_turn_of_new_groups_under_header_style_keys(ctx):
     c = Case(gkey[of], sizes[of], np.roll(gkey, 777), np.ones(n_groups), np.zeros(n_groups),
              hash_only=True)
     assert c.w_cnt[:5].tolist() == [0, of.size, 0, n_groups, 0]
+    run(ctx, c, modes=(0,))
+
+
+@gpu
+def test_packets_beyond_one_grid(ctx):
+    """one packet more than the probe and emit grids take in a trip, in a
+    shuffled turn of 150,000 open groups and 100,000 new ones over 300,000
+    slots, half of them free: the last packet is the only one of its group,
+    which the first workgroup's second trip finds new and opens.  Many keys, so
+    under the hash only."""
+    n, n_slots = grid_wrap(), 300000
+    grid = ncu() * GRID_PER_CU * TILE
+    assert n > grid, "the packets no longer make the grid loop"
+    rng = np.random.default_rng(4650)
+    g = rng.permutation(250001).astype(np.uint64)
+    gkey = ((g % np.uint64(4096)) << np.uint64(40)) | (g // np.uint64(4096) + np.uint64(1))
+    open_keys, new_keys, lone = gkey[:150000], gkey[150000:250000], gkey[250000]
+    acc_len = np.zeros(n_slots, np.int64)
+    taken = rng.permutation(n_slots)[:150000]
+    acc_len[taken] = rng.integers(1, 1400, 150000)
+    slot_key = new_keys[rng.integers(0, new_keys.size, n_slots)]  # (the free slots': stale)
+    slot_key[taken] = open_keys
+    key = np.where(rng.random(n) < 0.5, open_keys[rng.integers(0, open_keys.size, n)],
+                   new_keys[rng.integers(0, new_keys.size, n)])
+    key[n - 1] = lone
+    c = Case(key, rng.integers(0, 256, n), slot_key, rng.integers(0, 256, n_slots), acc_len,
+             hash_only=True)
+    assert c.w_cnt[AS.OPENED] > 90000 and c.w_cnt[AS.AWAY] == 0 and c.w_cnt[AS.OPEN] > grid // 3
+    at = int(c.w_out[n - 1])
+    assert at < n_slots and acc_len[at] == 0 and c.w_slot_key[at] == lone != c.slot_key[at]
+    assert c.w_slot_k[at] == c.k[n - 1]
     run(ctx, c, modes=(0,))
 
 

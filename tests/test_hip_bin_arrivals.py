@@ -17,6 +17,7 @@ import pytest
 import bin_rule as B
 from libquic_amd import qfec
 from test_hip_accumulate_ragged import dview
+from turn_sizes import GRID_PER_CU, grid_wrap, ncu
 
 gpu = pytest.mark.gpu
 POISON = 0xA5
@@ -192,6 +193,33 @@ def test_more_tiles_than_one_scan_pass(ctx):
     slot[:5] = [0, n_slots - 1, TILE * SCAN_BLOCK - 1, TILE * SCAN_BLOCK, n_slots - 1]
     got, e = run(ctx, Arrivals(rng, slot), n_slots)
     assert got["ptr"][n_slots] == n and e.long.size == 0
+
+
+@gpu
+def test_packets_beyond_one_grid(ctx):
+    """one packet more than the count and scatter grids take in a trip: the
+    last packet is ranked and placed by the first workgroup's second trip, and
+    leaves its slot behind the packets the first trip's workgroups brought"""
+    n, n_slots = grid_wrap(), 16384
+    grid = ncu() * GRID_PER_CU * TILE
+    assert n > grid, "the packets no longer make the grid loop"
+    rng = np.random.default_rng(5150)
+    slot = rng.integers(0, n_slots, n).astype(np.uint32)
+    slot[rng.random(n) < 0.05] = B.NO_SLOT
+    bad = rng.integers(0, n - 1, 6)
+    slot[bad] = [n_slots, n_slots + 1, 1 << 20, 1 << 31, 0xFFFFFFFE, n_slots]
+    s = 4099
+    slot[n - 1] = s
+    a = Arrivals(rng, slot)
+    e = Expect(a, n_slots)
+    assert e.long.size == 0 and int(e.cnt[2]) == 6
+    mine = e.src[int(e.ptr[s]):int(e.ptr[s + 1])]
+    assert mine.size > 1 and mine[0] < grid <= mine[-1] == n - 1
+    o = launch(ctx, a, n_slots)
+    with pytest.raises(qfec.InvalidFecData):
+        ctx.sync()
+    compare(fetch(o), e)
+    assert ctx.sync() == qfec.QFEC_OK
 
 
 # ---- 3. stability across workgroups ----------------------------------------------------------

@@ -1,12 +1,16 @@
 """qfec_build_acks on the GPU, whole buffers bit for bit against the rule of
 tests/ack_rule.py: the ack's scalars, both CSR tables, their tails and the
-state untouched (ack_device.py)."""
+state untouched (ack_device.py).  Beyond one trip of the scan over the acks
+and beyond one full grid of waves the expectation is the whole-array rule, tied
+to the sequential one on a sample of the same acks."""
 import numpy as np
 import pytest
 
 import ack_cases as K
 import ack_device as D
 import ack_rule as A
+from test_ack_rule import both_build
+from turn_sizes import GRID_PER_CU, SCAN_BLOCK, TILE, ncu, wave_wrap
 
 gpu = pytest.mark.gpu
 U64 = np.uint64
@@ -108,6 +112,75 @@ def test_random_states(ctx, window, n_conns, max_ranges, max_revived):
         assert want["truncated"].any()
     if window > 64:  # a walk of more than one trip
         assert int((state["largest"] - np.maximum(state["least"], U64(1))).max()) > 64
+
+
+_big = {}
+
+
+def big_state():
+    """more connections than acks_walk_kernel's grid has waves, at window 64"""
+    if not _big:
+        n_conns = wave_wrap() + 40
+        _big["state"] = K.grown_state(np.random.default_rng(6100), n_conns)
+    return _big["state"]
+
+
+def rows_of(ptr, table, acks):
+    """the rows of a CSR table that belong to `acks`, in their order"""
+    _, at, _ = A._ranges(ptr[:-1][acks], np.diff(ptr.astype(np.int64))[acks])
+    return table[at.astype(np.int64)]
+
+
+def run_big(ctx, ack_conn, max_ranges, max_revived):
+    """the whole-array rule as the expectation, tied to the sequential one on
+    300 of the same acks (the last among them)"""
+    state = big_state()
+    want = A.build_acks_np(state, ack_conn, max_ranges, max_revived)
+    acks = np.unique(np.r_[np.random.default_rng(len(ack_conn)).integers(0, len(ack_conn), 299),
+                           len(ack_conn) - 1])
+    some = both_build(state, ack_conn[acks], max_ranges, max_revived)
+    for k in ("largest", "hash", "truncated"):
+        assert np.array_equal(some[k], want[k][acks]), k
+    for ptr, tables in (("range_ptr", ("range_lo", "range_hi")), ("rev_ptr", ("rev_pn",))):
+        assert np.array_equal(np.diff(some[ptr]), np.diff(want[ptr])[acks]), ptr
+        for t in tables:
+            assert np.array_equal(some[t], rows_of(want[ptr], want[t], acks)), t
+    D.build(ctx, D.DevState(state), ack_conn, max_ranges, max_revived, want)
+    return want
+
+
+@gpu
+@pytest.mark.parametrize("max_ranges,max_revived", [(3, 2), (255, 0), (1, 255)])
+@pytest.mark.parametrize("n_acks", [SCAN_BLOCK, SCAN_BLOCK + 1, 2 * SCAN_BLOCK + 1])
+def test_acks_beyond_one_scan_trip(ctx, n_acks, max_ranges, max_revived):
+    """acks_scan_kernel scans range_ptr and rev_ptr, an ack a lane: from 1,025
+    acks on both take a second trip with the first one's sum as its base (1,024
+    acks fill one trip exactly: nothing lies behind entry 1,024 there)"""
+    rng = np.random.default_rng(n_acks + max_ranges)
+    state = big_state()
+    conn = K.acks_ending_full(rng, state, n_acks, max_ranges, max_revived)
+    conn[n_acks // 2:-1:3] = conn[:(n_acks - 1 - n_acks // 2 + 2) // 3]  # connections repeat
+    assert np.unique(conn).size < n_acks - 100
+    want = run_big(ctx, conn, max_ranges, max_revived)
+    for ptr in ["range_ptr"] + (["rev_ptr"] if max_revived else []):
+        assert want[ptr][SCAN_BLOCK] > 0, ptr
+        if n_acks > SCAN_BLOCK:
+            assert want[ptr][-1] - want[ptr][SCAN_BLOCK] > 0, \
+                ptr + ": the acks no longer make the scan take a second trip"
+    assert max_revived or want["rev_ptr"][-1] == 0
+
+
+@gpu
+def test_acks_beyond_one_grid(ctx):
+    """one ack more than acks_walk_kernel's grid has waves: the first wave's
+    second trip walks the last ack, a truncated one with revived packets"""
+    n_acks = wave_wrap()
+    assert n_acks > ncu() * GRID_PER_CU * TILE // 64, "the acks no longer make the grid loop"
+    conn = K.acks_ending_full(np.random.default_rng(6200), big_state(), n_acks, 3, 2,
+                              truncated=True)
+    want = run_big(ctx, conn, 3, 2)
+    assert want["truncated"][-1] == 1 and want["rev_ptr"][-1] > want["rev_ptr"][-2]
+    assert want["range_ptr"][-1] - want["range_ptr"][-2] == 3
 
 
 @gpu

@@ -234,6 +234,23 @@ def test_all_one_status(ctx, kind):
     assert not rows.acc_len.any()
 
 
+def classify_one_byte(maps, k=7):
+    """status and revived_idx of groups of k = 7 from their one map byte, over
+    the whole array; tied to the rule on every 257th group and the last"""
+    n = len(maps)
+    data = maps[:, 0] & 0x7F
+    miss = k - np.unpackbits(data[:, None], axis=1).sum(axis=1)
+    fec = maps[:, 0] >> 7
+    st = np.where(miss == 0, R.COMPLETE, np.where((miss == 1) & (fec == 1), R.REVIVED,
+                                                  R.UNREVIVABLE)).astype(np.uint8)
+    first = np.array([[i for i in range(8) if not (v >> i) & 1][0] if v != 0xFF else 0xFF
+                      for v in range(256)], np.uint8)[data | 0x80]
+    idx = np.where(st == R.REVIVED, first, 0xFF).astype(np.uint8)
+    for g in list(range(0, n, 257)) + [n - 1]:
+        assert R.classify(maps[g], k) == (int(st[g]), int(idx[g]))
+    return st, idx
+
+
 @gpu
 def test_second_scan_tile(ctx):
     """256 * 1024 + 1 groups of 16-B rows: the scan kernel's second tile.  The
@@ -243,16 +260,7 @@ def test_second_scan_tile(ctx):
     n, k = 256 * 1024 + 1, 7
     maps = rng.integers(0, 256, (n, 1), dtype=np.uint8)
     maps[rng.integers(0, n, n // 2), 0] |= 0x7F  # more complete groups than chance gives
-    data = maps[:, 0] & 0x7F
-    miss = k - np.unpackbits(data[:, None], axis=1).sum(axis=1)
-    fec = maps[:, 0] >> 7
-    st = np.where(miss == 0, R.COMPLETE, np.where((miss == 1) & (fec == 1), R.REVIVED,
-                                                  R.UNREVIVABLE)).astype(np.uint8)
-    first = np.array([[i for i in range(8) if not (v >> i) & 1][0] if v != 0xFF else 0xFF
-                      for v in range(256)], np.uint8)[data | 0x80]
-    idx = np.where(st == R.REVIVED, first, 0xFF).astype(np.uint8)
-    for g in range(0, n, 257):
-        assert R.classify(maps[g], k) == (int(st[g]), int(idx[g]))
+    st, idx = classify_one_byte(maps, k)
     acc = rng.integers(0, 256, n * 16, dtype=np.uint8)
     acc_len = np.full(n, 16, np.uint16)
     rev = np.flatnonzero(st == R.REVIVED)

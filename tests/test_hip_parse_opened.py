@@ -18,6 +18,7 @@ import parse_rule as PR
 from libquic_amd import qfec
 from test_hip_accumulate_ragged import dview
 from test_parse_rule import check_against_reference, fixture_turn, random_turn
+from turn_sizes import TILE, grid_wrap  # packets per workgroup trip; one more than a full grid
 
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
@@ -25,7 +26,6 @@ POISON8 = np.uint8(0xA5)
 POISON16 = np.uint16(0xA5A5)
 POISON32 = np.uint32(0xA5A5A5A5)
 POISON64 = np.uint64(0xA5A5A5A5A5A5A5A5)
-TILE = 256  # packets per workgroup trip
 # what lies behind the arena's last byte: an in-group data header, offset 0
 BEYOND = np.array([0x03, 0x00, 0x11, 0x22, 0x33, 0x44, 0x55, 0x66], np.uint8)
 OUTPUTS = [("key", np.uint64, POISON64), ("idx", np.uint8, POISON8),
@@ -137,11 +137,6 @@ def test_reference_fixture(ctx, fixture, version):
     out = {name: host(d[name], dtype)[:c.n] for name, dtype, _ in OUTPUTS}
     check_against_reference(g, rows, out)
     assert len(rows) > 7000
-
-
-def grid_wrap():
-    """one packet more than a full grid of tiles: the first workgroup's second trip"""
-    return torch.cuda.get_device_properties(0).multi_processor_count * 16 * TILE + 1
 
 
 @gpu

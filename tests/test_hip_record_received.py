@@ -11,6 +11,7 @@ import pytest
 import ack_cases as K
 import ack_device as D
 import ack_rule as A
+from turn_sizes import GRID_PER_CU, TILE, grid_wrap, ncu, wave_wrap
 
 gpu = pytest.mark.gpu
 U64 = np.uint64
@@ -57,6 +58,75 @@ def test_random_turns(ctx, window, n_conns, n_packets, calls):
         assert (total > 0).all(), total
     if calls == 40:  # the ring went round several times
         assert int(state["largest"].min()) > 3 * window
+
+
+def last_of_each_recorded(state, turn):
+    """`turn` with its last packet, its last group and its last raise made ones
+    that change the state: the packet RECORDED, the group's revived packet a
+    missing one, the raise applied.  Each is asserted from the whole-array
+    rule; returns the rule's result over the turn."""
+    turn = {k: v.copy() if isinstance(v, np.ndarray) else v for k, v in turn.items()}
+    w, nc = state["window"], len(state["least"])
+    raised = np.zeros(nc + 1, bool)
+    raised[np.minimum(turn["raise_conn"], nc)] = True
+    # the packet: a number above the largest that no other packet of the turn
+    # brings, of a connection nobody raises
+    for c in np.flatnonzero(~raised[:nc]).tolist():
+        others = set(turn["packet_number"][:-1][turn["pkt_conn"][:-1] == c].tolist())
+        lo = max(int(state["least"][c]), 1)
+        ahead = set(range(max(int(state["largest"][c]) + 1, lo), lo + w)) - others
+        if ahead:  # (none where the window is full)
+            break
+    pn = min(ahead)
+    turn["pkt_conn"][-1], turn["packet_number"][-1], turn["hdr"][-1] = c, pn, 0
+    turn["entropy"][-1] = 1 << pn % 8
+    # the raise: one above the least of its connection (in range: not the first of the table)
+    r = int(turn["raise_conn"][-1])
+    assert r < nc
+    turn["raise_least"][-1] = int(state["least"][r]) + 1
+    # the group: without it first, to find a packet that stays missing and unrevived
+    turn["status"][-1] = 0
+    before = A.record_received_np(state, **turn)
+    st = before["state"]
+    live = A.live_cells(st)
+    lo = np.maximum(st["least"], U64(1))
+    gaps = []
+    for c2 in np.flatnonzero(~raised[:nc] & (st["largest"] > lo + U64(2))):
+        gaps = [q for q in range(int(lo[c2]), int(st["largest"][c2])) if live[c2, q % w] == 0]
+        if gaps:
+            break
+    free = np.setdiff1d(np.arange(len(turn["slot_key"])), turn["slot"])[0]
+    turn["status"][-1], turn["revived_idx"][-1], turn["slot"][-1] = A.GROUP_REVIVED, 0, free
+    turn["slot_key"][free] = c2 << K.KEY_SHIFT | gaps[0]
+    want = A.record_received_np(state, **turn)
+    assert want["rcv_out"][-1] == A.RECORDED
+    assert want["state"]["cells"][c, pn % w] == A.RECEIVED | A.ENTROPY
+    assert want["counts"][A.N_REVIVED] == before["counts"][A.N_REVIVED] + 1
+    assert want["state"]["cells"][c2, gaps[0] % w] == A.REVIVED
+    assert want["state"]["least"][r] == state["least"][r] + U64(1)
+    return turn, want
+
+
+@gpu
+def test_a_turn_beyond_one_grid(ctx):
+    """Two calls on one device state, each of one packet and one group more
+    than a full grid of lanes and one raise more than a full grid of waves: the
+    last packet, group and raise come in the first workgroup's second trip,
+    each changes the state, and the twelve tallies hold both trips' counts."""
+    n, n_raise = grid_wrap(), wave_wrap()
+    grid = ncu() * GRID_PER_CU * TILE
+    assert n - 1 >= grid and n_raise - 1 >= grid // 64, "the turn no longer makes the grids loop"
+    rng = np.random.default_rng(6400)
+    state = A.new_state(n_raise + 40, 64)
+    dev = D.DevState(state)
+    total = np.zeros(12, U64)
+    for call in range(2):
+        turn = K.random_turn(rng, state, n, n_groups=n, n_raise=n_raise, bad_conn=call == 1)
+        turn, want = last_of_each_recorded(state, turn)
+        assert want["latched"] == (call == 1)
+        D.record(ctx, dev, turn, want)
+        state, total = want["state"], total + want["counts"]
+    assert (total > 0).all(), total
 
 
 @gpu

@@ -18,6 +18,7 @@ import retire_rule as RR
 from libquic_amd import qfec
 from test_hip_accumulate_ragged import dview
 from test_retire_rule import EDGES, K, make_keys, random_case
+from turn_sizes import GRID_PER_CU, grid_wrap, ncu
 
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
@@ -155,6 +156,17 @@ def test_parameters(ctx, n_conns, max_groups, shift):
 def test_packets_beyond_one_scan_pass(ctx):
     rng = np.random.default_rng(5200)
     run(ctx, Case(random_case(rng, BIG, 300, 300, 40, 2, runs=True)))
+
+
+@gpu
+def test_packets_beyond_one_grid(ctx):
+    """one packet more than the filter's grid takes in a trip: the last packet
+    is judged by the first workgroup's second trip and counted with its first"""
+    n = grid_wrap()
+    assert n > ncu() * GRID_PER_CU * TILE, "the packets no longer make the grid loop"
+    c = Case(random_case(np.random.default_rng(5250), n, 300, 300, 40, 2, runs=True))
+    assert (c.w_cnt[:5] > 0).sum() >= 3, c.w_cnt
+    run(ctx, c)
 
 
 @gpu

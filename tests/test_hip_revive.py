@@ -19,6 +19,7 @@ import torch
 from oracle import oracle_c as OC
 from oracle import qfec_np as Q
 from libquic_amd import qfec
+from turn_sizes import SCAN_BLOCK, SCAN_WRAP, TILE
 
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
@@ -275,9 +276,28 @@ def order_kinds(pattern, n, rng):
                                        (100003, "alternating"), (1, "alternating"),
                                        (1, "random"), (257, "random"), (257, "alternating")])
 def test_list_order(ctx, n, pattern):
-    k, L = 4, 32
     rng = np.random.default_rng(n + len(pattern))
-    kinds = order_kinds(pattern, n, rng)
+    run_list_order(ctx, order_kinds(pattern, n, rng), 4, 32, rng)
+
+
+@gpu
+def test_groups_beyond_one_scan_trip(ctx):
+    """256 * 1024 + 1 groups of the smallest rows: the scan over the 1,025 tiles
+    takes a second trip, and the last group, a revived one, gets its place in
+    the list and the three counts from the base and the side sums carried into
+    it"""
+    n = SCAN_WRAP
+    assert (n + TILE - 1) // TILE > SCAN_BLOCK, "the groups no longer make the scan take a second trip"
+    rng = np.random.default_rng(n)
+    kinds = order_kinds("random", n, rng)
+    kinds[n - 1] = 1
+    edge = SCAN_BLOCK * TILE
+    assert set(kinds[edge - TILE:edge].tolist()) == {0, 1, 2} == set(kinds[:TILE].tolist())
+    run_list_order(ctx, kinds, 2, 16, rng)
+
+
+def run_list_order(ctx, kinds, k, L, rng):
+    n = kinds.size
     data, fec = maps_from_kinds(kinds, k, rng)
     case = Case(data, fec, L, 4242 + n)
     assert np.array_equal(case.status, kinds.astype(np.uint8))

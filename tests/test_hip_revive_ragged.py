@@ -21,6 +21,7 @@ import torch
 
 from oracle import oracle_c as OC
 from libquic_amd import qfec
+from turn_sizes import SCAN_BLOCK, SCAN_WRAP, TILE
 
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
@@ -416,6 +417,25 @@ def test_large_batch(ctx, pattern):
         kinds[:5000] = 1
     b = Batch(tiny_specs(n, kinds, rng), 62)
     assert b.counts[1] == int((kinds == 1).sum()) >= 5000
+    run(ctx, b)
+
+
+@gpu
+def test_groups_beyond_one_scan_trip(ctx):
+    """256 * 1024 + 1 groups: the scan over the 1,025 tiles takes a second trip,
+    and the last group, a revived one, gets its place in the list and the three
+    counts from the base and the side sums carried into it"""
+    n = SCAN_WRAP
+    assert (n + TILE - 1) // TILE > SCAN_BLOCK, "the groups no longer make the scan take a second trip"
+    rng = np.random.default_rng(63)
+    # (few lost packets: the batch's per-packet loops on the host are what the test costs)
+    kinds = np.where(rng.random(n) < 0.9, 0, 2)
+    kinds = np.where(rng.random(n) < 0.04, 1, kinds)
+    kinds[n - 1] = 1
+    edge = SCAN_BLOCK * TILE
+    assert set(kinds[edge - TILE:edge].tolist()) == {0, 1, 2} == set(kinds[:TILE].tolist())
+    b = Batch(tiny_specs(n, kinds, rng), 64)
+    assert b.counts[1] == int((kinds == 1).sum()) and b.lst[-1] == n - 1
     run(ctx, b)
 
 

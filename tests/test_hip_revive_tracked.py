@@ -16,7 +16,8 @@ import admit_rule as R
 from libquic_amd import qfec
 from test_hip_accumulate_ragged import dview
 from test_hip_close_accumulated import (MSG as CLOSE_MSG, PAD, POISON, POISON16, POISON64, Rows,
-                                        host, make_maps, place, same)
+                                        classify_one_byte, host, make_maps, place, same)
+from turn_sizes import SCAN_BLOCK, SCAN_WRAP, TILE
 import close_rule as CR
 
 gpu = pytest.mark.gpu
@@ -139,6 +140,54 @@ def test_shapes(ctx, n, mode):
     assert not errs.any()
     for g in range(n):  # fresh slots are unrevivable whatever their stale maps say
         assert st[g] == (R.UNREVIVABLE if g in fresh else kinds[g])
+
+
+@gpu
+def test_groups_beyond_one_scan_trip(ctx):
+    """256 * 1024 + 1 groups of 16-B rows, K = 7 and one map byte by slot: the
+    scan over the 1,025 tiles takes a second trip, and the last group, a
+    revived one, gets its place in the list and the three counts from the base
+    and the side sums the scan carried into it.  The expectation is
+    test_hip_close_accumulated's vectorised one; qfec_revive_accumulated on the
+    same inputs gives the same buffers."""
+    rng = np.random.default_rng(2600)
+    n, k = SCAN_WRAP, 7
+    assert (n + TILE - 1) // TILE > SCAN_BLOCK, "the groups no longer make the scan take a second trip"
+    maps = rng.integers(0, 256, (n + 1, 1), dtype=np.uint8)
+    maps[rng.integers(0, n, n // 2), 0] |= 0x7F  # more complete groups than chance gives
+    maps[n - 1, 0], maps[n, 0] = 0xFF & ~0x08, POISON  # the last group revived; the row nobody owns
+    st, idx = classify_one_byte(maps[:n], k)
+    edge = SCAN_BLOCK * TILE
+    assert set(st[edge - TILE:edge].tolist()) == {0, 1, 2} and st[n - 1] == CR.REVIVED
+    assert idx[n - 1] == 3
+    acc = rng.integers(0, 256, n * 16, dtype=np.uint8)
+    rev = np.flatnonzero(st == CR.REVIVED)
+    want = dict(out=np.full(n * 16 + 32, PAD, np.uint8), st=st, idx=idx,
+                olen=np.where(st == CR.REVIVED, 16, 0).astype(np.uint16),
+                rlist=np.full(n, POISON64, np.uint64),
+                cnt=np.array([(st == s).sum() for s in range(3)], np.uint64))
+    want["out"][:n * 16].reshape(n, 16)[rev] = acc.reshape(n, 16)[rev]
+    want["rlist"][:rev.size] = rev
+    want_len = np.where(st != CR.UNREVIVABLE, 0, 16).astype(np.uint16)
+    d_acc, d_off = dview(acc), dview(np.arange(n, dtype=np.uint64) * np.uint64(16))
+    d_len, d_len2 = dview(np.full(n, 16, np.uint16)), dview(np.full(n, 16, np.uint16))
+    d_k, d_maps = dview(np.full(n, k, np.uint8)), dview(maps)
+    a, b = outputs(n, n * 16 + 32), outputs(n, n * 16 + 32)
+    ctx.revive_tracked(d_acc, 16, d_len, d_maps, 1, d_k, n, a["out"], d_off, a["olen"],
+                       status=a["st"], slot=None, n_slots=n, release_mask=0b011,
+                       revived_idx=a["idx"], revived_list=a["rlist"], counts=a["cnt"])
+    ctx.revive_accumulated(d_acc, 16, d_len2, d_k, d_maps, 1, n, b["out"], d_off, b["olen"],
+                           status=b["st"], slot=None, n_slots=n, release_mask=0b011,
+                           revived_idx=b["idx"], revived_list=b["rlist"], counts=b["cnt"])
+    ctx.sync()
+    for name, dt in (("st", np.uint8), ("olen", np.uint16), ("idx", np.uint8),
+                     ("rlist", np.uint64), ("cnt", np.uint64), ("out", np.uint8)):
+        same(name, host(a[name], dt), want[name])
+        same(name + " against revive_accumulated", host(a[name], dt), host(b[name], dt))
+    same("acc_len", host(d_len, np.uint16), want_len)
+    same("acc_len against revive_accumulated", host(d_len, np.uint16), host(d_len2, np.uint16))
+    same("acc", host(d_acc, np.uint8), acc)
+    same("maps", host(d_maps, np.uint8).ravel(), maps.ravel())
 
 
 # ---- 2. release masks ---------------------------------------------------------------------------------

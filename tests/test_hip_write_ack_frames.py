@@ -6,10 +6,12 @@ the comparison.  The rule itself is pinned to the reference framer on the CPU
 import numpy as np
 import pytest
 
+import ack_cases as C
 import ack_rule as A
 import ackwire_cases as K
 import ackwire_device as W
 import ackwire_rule as R
+from turn_sizes import GRID_PER_CU, TILE, ncu, wave_wrap
 
 gpu = pytest.mark.gpu
 
@@ -48,6 +50,41 @@ def test_ack_counts(ctx, n_acks):
     off, size = W.slots(cap)
     want = W.write(ctx, batch, state["cells"], 256, off, cap, size, prefix_len=2)
     assert (want["out_len"] == full + 2).all()
+
+
+@gpu
+def test_acks_beyond_one_grid(ctx):
+    """one ack more than ack_write_kernel's grid has waves, built from a state
+    of more connections than that at max_ranges 3, max_revived 2: the first
+    wave's second trip writes the last ack, a cut one, whose hash is walked
+    again there; the four tallies hold what both trips counted"""
+    n_acks, window = wave_wrap(), 64
+    assert n_acks > ncu() * GRID_PER_CU * TILE // 64, "the acks no longer make the grid loop"
+    rng = np.random.default_rng(6300)
+    state = C.grown_state(rng, n_acks + 39, window)
+    n_conns = len(state["least"])
+    conn = C.acks_ending_full(rng, state, n_acks, 3, 2, truncated=True)
+    conn[rng.integers(0, n_acks - 1, n_acks // 50)] = n_conns + 2
+    batch = A.build_acks_np(state, conn, 3, 2)
+    batch["ack_conn"] = conn
+    batch["delay"] = rng.choice(np.array(K.DELAYS, np.uint64), n_acks)
+    full = K.frame_sizes(batch, state["cells"], window)
+    cap = np.choose(rng.integers(0, 3, n_acks), [full, full - 1, 3])
+    # the last ack lists revived packets, which the writer drops first: the
+    # largest room at which it cuts a range as well
+    ack = R.ack_of(batch, n_acks - 1)
+    for room in range(int(full[-1]) - 1, 0, -1):
+        w = R.write_ack_frame(cap=room, entropy_up_to=lambda pn: 0, **ack)
+        if w["cut"] and w["frame"]:
+            break
+    cap[-1] = room
+    cap = np.maximum(cap, 0).astype(np.uint16)
+    off, size = W.slots(cap)
+    want = R.write_ack_frames_np(batch, state["cells"], window, np.full(size, W.POISON8), off, cap)
+    assert want["latched"] and (want["counts"] > 0).all(), want["counts"]
+    assert set(want["status"].tolist()) == {R.WRITTEN, R.CUT, R.NO_ROOM, R.RANGE}
+    assert want["status"][-1] == R.CUT and want["wire_largest"][-1] < batch["largest"][-1]
+    W.write(ctx, batch, state["cells"], window, off, cap, size, want=want)
 
 
 @gpu

@@ -12,6 +12,7 @@ import parse_rule as PR
 from libquic_amd import qfec
 from test_hip_accumulate_ragged import dview
 from test_hip_parse_opened import POISON8, POISON64, TILE, host, same, tail
+from turn_sizes import GRID_PER_CU, grid_wrap, ncu
 
 gpu = pytest.mark.gpu
 FILL = 0xEE
@@ -79,6 +80,23 @@ def test_sizes_and_surroundings(ctx, n):
     hdr = np.where(rng.random(n) < 0.9, rng.integers(0, 8, n), rng.integers(8, 256, n))
     off, size = layout(n, rng)
     run(ctx, off, hdr.astype(np.uint8), rng.integers(0, 256, n).astype(np.uint8), size, 31)
+
+
+@gpu
+def test_records_beyond_one_grid(ctx):
+    """one record more than the grid takes in a trip: the last record, a
+    refused one, is the first workgroup's second trip -- nothing written for
+    it, and counted with the refused ones of the first trip"""
+    n = grid_wrap()
+    assert n > ncu() * GRID_PER_CU * TILE, "the records no longer make the grid loop"
+    rng = np.random.default_rng(9050)
+    hdr = np.where(rng.random(n) < 0.9, rng.integers(0, 8, n), rng.integers(8, 256, n))
+    hdr[n - 2:] = 3, 0x1F
+    off, size = layout(n, rng)
+    d, want, cnt = run(ctx, off, hdr.astype(np.uint8), rng.integers(0, 256, n).astype(np.uint8),
+                       size, 31)
+    assert cnt[0] > n // 2 and cnt[1] > n // 20
+    assert np.all(want[int(off[n - 1]):] == FILL) and want[int(off[n - 2])] != FILL
 
 
 @gpu
