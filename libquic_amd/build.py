@@ -16,9 +16,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libqfec.so")
 ARCH = os.environ.get("QFEC_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["qfec_kernels.hip", "qpp_kernels.hip", "qent_kernels.hip", "qfec_capi.cpp", "quic_fec_group.cc",
-           "quic_fec_wire.cc", "quic_fec_connection.cc"]
-HEADERS = ["qfec_internal.h", "quic_fec_group.h", "quic_fec_wire.h", "quic_fec_connection.h"]
+SOURCES = ["qfec_kernels.hip", "qturn_kernels.hip", "qpp_kernels.hip", "qent_kernels.hip", "qfec_capi.cpp",
+           "quic_fec_group.cc", "quic_fec_wire.cc", "quic_fec_connection.cc"]
+HEADERS = ["qfec_internal.h", "qfec_device.h", "quic_fec_group.h", "quic_fec_wire.h",
+           "quic_fec_connection.h"]
 
 
 def hipcc() -> str:
@@ -118,6 +119,10 @@ def build_cpp_tests(force: bool = False) -> list:
 # (tools/tune): rebuilt whenever those change, so a tool never runs with a
 # stale view of a class layout (round 4: host_cost built before a
 # QuicFecGroup layout change corrupted its heap on the GPU box).
+# A .hip tool is about the XOR kernels and is rebuilt when qfec_kernels.hip
+# changes.  It includes qturn_kernels.hip too, only to link (the XOR file's
+# revive launches call into it), and launches none of its kernels: an edit
+# there rebuilds no tool.
 TOOLS = [("host_cost.cc", False), ("pcie_duplex.hip", True), ("phased_copy.hip", True),
          ("null_phased.hip", True)]
 

@@ -1,6 +1,7 @@
 // qfec_capi.cpp — the C-ABI (include/qfec.h): context, argument validation,
 // error mapping, the host-pointer (pinned, chunked, overlapped) path and the
-// dispatch to the gfx950 kernels in qfec_kernels.hip.
+// dispatch to the gfx950 kernels: the XOR path in qfec_kernels.hip, the table
+// passes of the receiver's turn in qturn_kernels.hip.
 //
 // Error behaviour mirrors QuicFramer: a bool-style failure with a QuicErrorCode
 // and a detailed string (quic_framer.cc:1128-1135 set_detailed_error +

@@ -1,5 +1,9 @@
 // qfec_internal.h — launch interface between the C-ABI (qfec_capi.cpp) and
-// the gfx950 kernels (qfec_kernels.hip).  Not installed; not part of the ABI.
+// the gfx950 kernels (qfec_kernels.hip: the XOR path; qturn_kernels.hip: the
+// table passes of the receiver's turn; qpp_kernels.hip, qent_kernels.hip).
+// Host and device compilers both read it: no device intrinsics here (the
+// device code that kernel files share is in qfec_device.h).  Not installed; not
+// part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -261,6 +265,15 @@ hipError_t launch_close_revive(const CloseArgs& a, hipStream_t s);
 struct TrackedCloseArgs : CloseArgs {};
 // Launches as launch_close_revive.  n_groups > 0.
 hipError_t launch_tracked_revive(const TrackedCloseArgs& a, hipStream_t s);
+
+// The first three launches of the four revives above (classify, scan, emit):
+// the work list and its length, left on the device.  Defined with the turn
+// passes (qturn_kernels.hip); the launch_*revive* functions call it and then
+// launch their own kernel over the list (qfec_kernels.hip).  n_groups > 0.
+hipError_t launch_revive_passes(const ReviveArgs& a, hipStream_t s);
+hipError_t launch_revive_passes(const ReviveRaggedArgs& a, hipStream_t s);
+hipError_t launch_revive_passes(const CloseArgs& a, hipStream_t s);
+hipError_t launch_revive_passes(const TrackedCloseArgs& a, hipStream_t s);
 
 // qfec_admit_ragged: filter a turn's candidates against the per-slot running
 // maps and the open call's ok flags, and write the CSR tables the accumulate

@@ -15,7 +15,7 @@ def source(name):
 
 
 def test_constants_are_the_sources():
-    header, kernels = source("qfec_internal.h"), source("qfec_kernels.hip")
+    header, kernels = source("qfec_internal.h"), source("qturn_kernels.hip")
     tile = re.findall(r"constexpr\s+uint32_t\s+kReviveTile\s*=\s*(\d+)\s*;", header)
     block = re.findall(r"constexpr\s+int\s+kRvScanBlock\s*=\s*(\d+)\s*;", kernels)
     grid = re.findall(r"inline\s+uint32_t\s+per_packet_grid\s*\([^)]*\)\s*\{[^}]*?"

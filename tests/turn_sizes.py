@@ -1,5 +1,5 @@
 """The sizes at which a receive-turn pass takes a second trip of one of its two
-loops (libquic_amd/csrc/qfec_kernels.hip), for the tests that run every call
+loops (libquic_amd/csrc/qturn_kernels.hip), for the tests that run every call
 past them.  tests/test_turn_sizes.py pins the constants to the sources.
 
 The one-workgroup scan (tile_scan) takes a trip per SCAN_BLOCK elements and

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 kernels of two builds of one source file by symbol.
+"""Compare the gfx950 kernels of two builds by symbol.
 
 The check behind every "the earlier kernels are unchanged" in DESIGN.md.  Build
 the assembly of both commits (the parent's from a `git worktree` or an
@@ -8,6 +8,13 @@ exported copy):
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include --cuda-device-only -S \\
         libquic_amd/csrc/qfec_kernels.hip -o head.s
     python tools/kernel_diff.py parent.s head.s
+
+A side with several kernel files (qfec_kernels.hip and qturn_kernels.hip; a
+commit that moves kernels from one file to another) is their assembly files
+concatenated, `cat xor.s turn.s > head.s`: kernels are paired by symbol
+wherever they stand, and no two files define one kernel.  A change that edits
+one kernel file and no header compares that file alone: the other file's
+kernels are compiled from text it did not touch.
 
 A kernel's stream is what libquic_amd/isa_guard.py cuts from its symbol's label
 to its .Lfunc_end, comments dropped, with the function numbers taken out of the

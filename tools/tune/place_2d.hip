@@ -6,6 +6,8 @@
 // buffer; a parity-driven one as a parity column slow with every rows.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/tune/place_2d.hip -o tools/tune/build/place_2d
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
+// (its launch_*revive* functions call launch_revive_passes, defined here)
+#include "../../libquic_amd/csrc/qturn_kernels.hip"
 
 #include <algorithm>
 #include <cstdio>

@@ -8,6 +8,8 @@
 // be matched to the destination (tools/place_pmc.py).
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/tune/place_pmc.hip -o tools/tune/build/place_pmc
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
+// (its launch_*revive* functions call launch_revive_passes, defined here)
+#include "../../libquic_amd/csrc/qturn_kernels.hip"
 
 #include <cstdio>
 #include <cstdlib>

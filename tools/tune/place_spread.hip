@@ -6,6 +6,8 @@
 // parity destination of place_fixed: the product and S = 64, 512, 4096.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/tune/place_spread.hip -o tools/tune/build/place_spread
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
+// (its launch_*revive* functions call launch_revive_passes, defined here)
+#include "../../libquic_amd/csrc/qturn_kernels.hip"
 
 #include <algorithm>
 #include <cstdio>

@@ -5,6 +5,8 @@
 //
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/tune/tune_fixed.hip -o tools/tune/build/tune_fixed
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
+// (its launch_*revive* functions call launch_revive_passes, defined here)
+#include "../../libquic_amd/csrc/qturn_kernels.hip"
 
 #include <algorithm>
 #include <cstdio>

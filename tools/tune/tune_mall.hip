@@ -13,6 +13,8 @@
 //   tune_mall [reps=5] [rounds=3] [palign=16] [slot=1536]
 // Every phased variant is byte-compared with the one-pass product first.
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
+// (its launch_*revive* functions call launch_revive_passes, defined here)
+#include "../../libquic_amd/csrc/qturn_kernels.hip"
 
 #include <algorithm>
 #include <cstdio>

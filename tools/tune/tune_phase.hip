@@ -28,6 +28,8 @@
 // run:   tune_phase [launches per cell] [rounds] [groups]
 #define QFEC_PHASE_TUNE 1
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
+// (its launch_*revive* functions call launch_revive_passes, defined here)
+#include "../../libquic_amd/csrc/qturn_kernels.hip"
 
 #include <algorithm>
 #include <cstdio>

@@ -20,6 +20,8 @@
 //   tune_rphase [reps=5] [rounds=3] [palign=16] [slot=1536]
 // Outputs byte-compared with ragged_block_kernel (the product) first.
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
+// (its launch_*revive* functions call launch_revive_passes, defined here)
+#include "../../libquic_amd/csrc/qturn_kernels.hip"
 
 #include <algorithm>
 #include <cstdio>

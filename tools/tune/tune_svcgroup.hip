@@ -12,6 +12,8 @@
 // host or device memory.  Medians of 300 launches; outputs byte-checked.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I libquic_amd/csrc tools/tune/tune_svcgroup.hip -o tools/tune/build/tune_svcgroup
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
+// (its launch_*revive* functions call launch_revive_passes, defined here)
+#include "../../libquic_amd/csrc/qturn_kernels.hip"
 
 #include <algorithm>
 #include <cstdio>

@@ -8,6 +8,8 @@
 //   * ragged encode (configs[3] shapes) with packet bytes on the host
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/tune/tune_zero_copy.hip -o tools/tune/build/tune_zero_copy
 #include "../../libquic_amd/csrc/qfec_kernels.hip"
+// (its launch_*revive* functions call launch_revive_passes, defined here)
+#include "../../libquic_amd/csrc/qturn_kernels.hip"
 
 #include <chrono>
 #include <cstdio>
