@@ -150,31 +150,33 @@ def synth_fixed(seed, g0, n, k, L, row_stride=None, group_stride=None):
     return rows
 
 
-def encode_fixed(rows, k, L, n, row_stride=None, group_stride=None, parity_stride=None):
+def encode_fixed(rows, k, L, n, row_stride=None, group_stride=None, parity_stride=None, fill=0):
+    """fill: what the bytes the call does not write hold (here and below: the
+    oracle writes exactly the L or parity_len[g] bytes of each group)"""
     rs = L if row_stride is None else row_stride
     gs = k * rs if group_stride is None else group_stride
     ps = L if parity_stride is None else parity_stride
-    par = np.zeros(n * ps, dtype=np.uint8)
+    par = np.full(n * ps, fill, dtype=np.uint8)
     rc = lib().qo_encode_fixed(_p(rows), k, L, rs, gs, n, _p(par), ps)
     return rc, par
 
 
 def recover_fixed(rows, parity, missing, k, L, n, row_stride=None, group_stride=None,
-                  parity_stride=None, out_stride=None):
+                  parity_stride=None, out_stride=None, fill=0):
     rs = L if row_stride is None else row_stride
     gs = k * rs if group_stride is None else group_stride
     ps = L if parity_stride is None else parity_stride
     os_ = L if out_stride is None else out_stride
-    out = np.zeros(n * os_, dtype=np.uint8)
+    out = np.full(n * os_, fill, dtype=np.uint8)
     missing = np.ascontiguousarray(missing, dtype=np.uint8)
     rc = lib().qo_recover_fixed(_p(rows), _p(parity), _p(missing), k, L, rs, gs, ps, n,
                                 _p(out), os_)
     return rc, out
 
 
-def encode_ragged(data, pkt_off, pkt_len, grp_ptr, parity_off, parity_size):
+def encode_ragged(data, pkt_off, pkt_len, grp_ptr, parity_off, parity_size, fill=0):
     n = grp_ptr.size - 1
-    par = np.zeros(parity_size, dtype=np.uint8)
+    par = np.full(parity_size, fill, dtype=np.uint8)
     plen = np.zeros(n, dtype=np.uint16)
     rc = lib().qo_encode_ragged(_p(data), _p(pkt_off), _p(pkt_len), _p(grp_ptr), n, _p(par),
                                 _p(parity_off), _p(plen))
@@ -182,9 +184,9 @@ def encode_ragged(data, pkt_off, pkt_len, grp_ptr, parity_off, parity_size):
 
 
 def recover_ragged(data, pkt_off, pkt_len, grp_ptr, parity, parity_off, parity_len, missing,
-                   out_off, out_size):
+                   out_off, out_size, fill=0):
     n = grp_ptr.size - 1
-    out = np.zeros(out_size, dtype=np.uint8)
+    out = np.full(out_size, fill, dtype=np.uint8)
     missing = np.ascontiguousarray(missing, dtype=np.uint8)
     rc = lib().qo_recover_ragged(_p(data), _p(pkt_off), _p(pkt_len), _p(grp_ptr), n, _p(parity),
                                  _p(parity_off), _p(parity_len), _p(missing), _p(out),

@@ -204,20 +204,25 @@ def test_host_pointer_path(ctx, pinned):
 
 
 def test_host_pointer_strided(ctx):
+    """whole buffers from a 0xA5 fill: a store into the gap between L and the
+    stride shows (tests/test_hip_host_fixed.py: the other staging branches)"""
     k, L, n = 5, 1350, 6000
     rs, ps = 1408, 1452
     rows = OC.synth_fixed(4, 0, n, k, L, row_stride=rs, group_stride=k * rs)
     miss = Q.drop_index(Q.SEED_DROP, np.arange(n), k).astype(np.uint8)
-    _, want_p = OC.encode_fixed(rows, k, L, n, rs, k * rs, ps)
-    par = np.zeros(n * ps, np.uint8)
+    _, want_p = OC.encode_fixed(rows, k, L, n, rs, k * rs, ps, fill=0xA5)
+    par = np.full(n * ps, 0xA5, np.uint8)
     ctx.encode(rows, k, L, n, par, row_stride=rs, group_stride=k * rs, parity_stride=ps,
                host=True)
     assert np.array_equal(par, want_p)
-    out = np.zeros(n * ps, np.uint8)
+    _, want_o = OC.recover_fixed(rows, want_p, miss, k, L, n, rs, k * rs, ps, ps, fill=0xA5)
+    out = np.full(n * ps, 0xA5, np.uint8)
     ctx.recover(rows, par, miss, k, L, n, out, row_stride=rs, group_stride=k * rs,
                 parity_stride=ps, out_stride=ps, host=True)
-    o = out.reshape(n, ps)[:, :L]
-    assert np.array_equal(o, rows.reshape(n, k, rs)[np.arange(n), miss, :L])
+    assert np.array_equal(out, want_o)
+    o = out.reshape(n, ps)
+    assert np.array_equal(o[:, :L], rows.reshape(n, k, rs)[np.arange(n), miss, :L])
+    assert (o[:, L:] == 0xA5).all()
 
 
 def test_host_invalid_missing(ctx):
